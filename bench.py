@@ -8,8 +8,14 @@ second summed over all ranks (weak scaling: every GPU runs its own batch stream,
 games shard across GPUs with no collective on the evaluation path).
 
 The headline dtype is ``f16x2``, the split-precision tower: inside the reference's own cross-runtime tolerance per leaf
-and, at search level, the visit distributions of the exact-f32 search.  Beside it the same JSON
-line carries
+and, at search level, the visit distributions of the exact-f32 search.
+
+A plain run does only what the headline needs: set-up, the settling steps and the W warm-up steps, the K timed steps, the
+outputs of the last timed step when ``--dump-outputs DIR`` is given (``DIR/policy.npy`` [batch, moves] logits and
+``DIR/value.npy`` [batch] values, float32; the inputs are seeded, so two builds can be compared output for output), and
+the result line.  With ``--full`` the same JSON line also carries
+  roofline                the tower kernel's event-timed launches, clock / power under load and the sustained MFMA rate
+  two_batches_in_flight   the same K steps on the evaluator's two lanes (``--lanes 2``)
   bf16                    the same steps on the bf16 tower (throughput mode, 8 significant bits), with its own roofline
   f16                     the same steps on the single-term f16 tower (throughput mode, 11 significant bits), with its own roofline
   f32                     the same steps on the exact-f32 tower (bit-identical to the CPU oracle), with its own roofline
@@ -19,8 +25,10 @@ line carries
   selfplay_full_games     whole games at a reduced simulation count (a measured games/hour)
   selfplay_config4        BASELINE config 4's shape: 64 concurrent games per GPU, records pooled over RCCL in the timed path
   cpu_baseline            the CPU path on this host's cores: evaluator (oracle C port and torch CPU) and search + oracle network
+  roofline_plane_pack     HBM roofline of the stand-alone plane-pack kernel
 
-    python bench.py                       # 1 GPU, defaults
+    python bench.py                       # 1 GPU, defaults: the headline only
+    python bench.py --full                # the headline and every measurement above
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -480,6 +488,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--dtype", choices=["f16x2", "bf16", "f16", "f32"], default="f16x2", help="tower of the headline `value` (default: the split-precision tower)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="chess20x256")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/policy.npy and DIR/value.npy (float32)")
+    ap.add_argument("--settle-seconds", type=float, default=0.4,
+                    help="untimed steps run for this long IN FRONT of the W warm-up steps (the clock governor needs longer than W steps to settle); 0 = none")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement behind the headline (roofline, two lanes, other towers, search agreement, self-play, "
+                         "plane pack, CPU baseline); the options below shape that part only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-smi", action="store_true", help="do not sample the device's clock / power under load beside the roofline")
     ap.add_argument("--lanes", type=int, choices=[1, 2], default=2,
@@ -490,13 +504,14 @@ def main():
     ap.add_argument("--no-f32", action="store_true", help="skip the f32 (bit-exact) object")
     ap.add_argument("--no-bf16", action="store_true", help="skip the bf16 (throughput mode) object")
     ap.add_argument("--no-f16", action="store_true", help="skip the f16 (single-term f16 throughput mode) object")
-    ap.add_argument("--settle-seconds", type=float, default=0.4,
-                    help="untimed steps run for this long IN FRONT of the W warm-up steps (the clock governor needs longer than W steps to settle); 0 = none")
-    ap.add_argument("--side-legs-timeout", type=float, default=900.0,
-                    help="seconds the legs behind the headline may take before a watchdog prints the line with what is there and ends the process")
+    ap.add_argument("--side-legs-timeout", type=float, default=480.0,
+                    help="seconds the legs behind the headline may take before a watchdog prints the line with what is there and ends the process "
+                         "(the default keeps a --full run inside 10 minutes; its legs take about 3)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             # `python bench.py --gpus N` without a launcher: this process -- which has not imported torch, loaded
@@ -533,7 +548,7 @@ def main():
     import torch.distributed as dist
 
     headline = args.workload == "chess20x256"
-    want_pg = world > 1 or (headline and args.selfplay_seconds > 0)  # config 4's leg pools records over RCCL, also on one rank
+    want_pg = world > 1 or (args.full and headline and args.selfplay_seconds > 0)  # config 4's leg pools records over RCCL, also on one rank
     pg_note = None
     if want_pg:
         import datetime
@@ -623,9 +638,11 @@ def main():
         except Exception:  # noqa: BLE001 - a diagnostic; the measurement does not depend on it
             return None
 
-    def time_evaluator(dtype, steps, warmup, lanes=1, settle_s=0.0):
+    def time_evaluator(dtype, steps, warmup, lanes=1, settle_s=0.0, extras=True, keep_outputs=False):
         """K steps of the hot path on the `dtype` tower -> dict(elapsed = seconds for the K steps (max over ranks),
-        launch_us = event-stamped tower launch duration, launches per step, ...)."""
+        launch_us = event-stamped tower launch duration, launches per step, ...).  `extras` = False leaves out everything
+        behind the timed steps (tower launch timing, clock and power, sustained MFMA rate, the two-lane pass); `keep_outputs`
+        adds the last timed step's (policy, value) as host arrays."""
         ev = HipEvaluator(blob, batch_size=batch, plane_words=plane_words, dtype=dtype, device=local_rank)
         d_policy = torch.empty((batch, d.moves), dtype=torch.float32, device=dev)
         d_value = torch.empty((batch,), dtype=torch.float32, device=dev)
@@ -663,16 +680,17 @@ def main():
         own_all = gather_over_ranks(own)
         # sanity: the timed kernels produced real numbers
         assert bool(torch.isfinite(d_policy).all()) and bool(torch.isfinite(d_value).all())
+        outputs = (d_policy.cpu().numpy(), d_value.cpu().numpy()) if keep_outputs else None
         # roofline of the dominant kernel (3x3 conv tower launch): event-stamped launch durations of the same
         # forward, taken right behind the timed region so that the device is in the same state as for `value`
-        launch_us, launches = ev.time_tower(batch, 20 if dtype != "f32" else 5) if rank == 0 else (0.0, 1)
+        launch_us, launches = ev.time_tower(batch, 20 if dtype != "f32" else 5) if rank == 0 and extras else (0.0, 1)
         # clock and power while the same steps keep running (sysfs, rank 0, best effort): the 2.5 PF peak is a
         # 2.4 GHz figure, and under its MFMA kernels the part holds less
-        smi = under_load_clock_and_power(step) if rank == 0 and not args.no_smi else None
+        smi = under_load_clock_and_power(step) if rank == 0 and extras and not args.no_smi else None
         # what THIS device's matrix pipe sustains on nothing but back-to-back MFMAs of the tower's kind (1 s; rank 0)
-        sustained = ev.mfma_sustained(1.0) if rank == 0 and not args.no_smi else None
+        sustained = ev.mfma_sustained(1.0) if rank == 0 and extras and not args.no_smi else None
         elapsed2 = None
-        if lanes == 2:
+        if lanes == 2 and extras:
             # the same K steps with two batches in flight (evaluator lanes 0/1 on two streams), as the self-play
             # driver runs the evaluator: one batch's kernel tails overlap the other's heads
             d_policy2, d_value2 = torch.empty_like(d_policy), torch.empty_like(d_value)
@@ -699,7 +717,7 @@ def main():
         kernel = ev.tower_kernel()
         ev.close()
         return dict(elapsed=elapsed, own_all=own_all, steps=steps, launch_us=launch_us, launches=launches, elapsed2=elapsed2, kernel=kernel,
-                    settle_steps=settle_steps, settle_ms=settle_ms, smi=smi, sustained=sustained)
+                    settle_steps=settle_steps, settle_ms=settle_ms, smi=smi, sustained=sustained, outputs=outputs)
 
     def roofline(dtype, r):
         """Dominant kernel = the tower conv launch.  `achieved` counts ALGORITHMIC flops (2 x multiply-adds of the
@@ -773,9 +791,16 @@ def main():
             "roofline": roofline(dtype, r),
         }
 
-    main_r = time_evaluator(args.dtype, args.steps, args.warmup, args.lanes, args.settle_seconds)
+    main_r = time_evaluator(args.dtype, args.steps, args.warmup, args.lanes, args.settle_seconds, extras=args.full,
+                            keep_outputs=rank == 0 and args.dump_outputs is not None)
+    if main_r["outputs"] is not None:
+        # the arrays a caller of cattus_hip_eval_device receives (at most 1,024 x 1,880 logits: under 8 MB per workload)
+        dump = Path(args.dump_outputs)
+        dump.mkdir(parents=True, exist_ok=True)
+        np.save(dump / "policy.npy", main_r["outputs"][0].astype(np.float32))
+        np.save(dump / "value.npy", main_r["outputs"][1].astype(np.float32))
 
-    # ---- the headline is complete here.  Everything behind it is a side leg: each runs inside run_leg(), so an exception
+    # ---- the headline is complete here.  Everything behind it (--full) is a side leg: each runs inside run_leg(), so an exception
     # becomes an {"error": ...} object in the line instead of taking the headline with it, and a watchdog prints the line
     # with what is there if the legs hang (a rank that died inside a collective of a leg leaves the others waiting).
     out = {}
@@ -798,7 +823,7 @@ def main():
             "config": {
                 "workload": f"{args.workload}: ConvNetV1 {d.blocks}x{d.filters}, board {d.board}, "
                 f"{d.planes} planes, {d.moves} moves, batch {batch} leaves/GPU, evaluator-only (planes, logits and values resident in HBM: "
-                "no PCIe, no search; the rate with both is `selfplay.node_evals_per_sec`)",
+                "no PCIe, no search; the rate with both is `selfplay.node_evals_per_sec` of --full)",
                 "per_gpu_batch": batch,
                 "flop_per_leaf": d.flops_per_position(),
             },
@@ -807,10 +832,11 @@ def main():
             # the slowest rank's time)
             "per_rank_value": [batch * args.steps / t for t in main_r["own_all"]],
             "effective_warmup_steps": args.warmup + main_r["settle_steps"],
-            "roofline": roofline(args.dtype, main_r),
             "host": {"cpus_of_this_rank": len(cpu_share), "ranks_on_this_node": local_world},
             "process_group": pg_note,
         }
+        if args.full:
+            out["roofline"] = roofline(args.dtype, main_r)
         out["whole_step_mfma_frac"] = d.flops_per_position() * batch / (main_r["elapsed"] / args.steps) / 1e12 / MFMA_PEAK_TFLOPS[args.dtype]
         if main_r["settle_ms"] is not None:
             out["settle"] = {"steps": main_r["settle_steps"], "ms_per_step": main_r["settle_ms"], "value": world * batch / (main_r["settle_ms"] * 1e-3),
@@ -860,7 +886,7 @@ def main():
             return None
 
     for dtype, skip, div in (("bf16", args.no_bf16, 1), ("f16", args.no_f16, 1), ("f32", args.no_f32, 10)):
-        if dtype == args.dtype or skip:
+        if dtype == args.dtype or skip or not args.full:
             continue
         k = max(5, args.steps // div)
 
@@ -900,7 +926,7 @@ def main():
                               "profiles/r03_search_agreement.json")
         return agreement
 
-    if headline and args.agreement_plies > 0 and rank == 0 and args.dtype != "f32":
+    if args.full and headline and args.agreement_plies > 0 and rank == 0 and args.dtype != "f32":
         obj = run_leg("search_agreement", agreement_leg)
         if obj is not None:
             out["search_agreement"] = obj
@@ -949,10 +975,10 @@ def main():
                           + ("" if pool else "; NO process group came up on this box (see process_group): nothing was pooled"))
         out["selfplay_config4"] = sp_c4
 
-    if headline and args.selfplay_seconds > 0:
+    if args.full and headline and args.selfplay_seconds > 0:
         run_leg("selfplay_legs", selfplay_legs)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         if headline:
             def pack_leg():
                 from cattus_amd import evaluator as ev_mod

@@ -2,7 +2,7 @@
 # A/B of two library builds over the bench's towers: scripts/ab_bench.sh OUTDIR ROUNDS VARIANT... ("" = the regular build)
 out=$1; rounds=$2; shift 2
 mkdir -p $out
-Q="--lanes 1 --settle-seconds 0.2 --no-cpu-baseline --selfplay-seconds 0 --agreement-plies 0 --no-f32 --no-bf16 --no-f16 --no-smi --steps 100 --warmup 10"
+Q="--full --lanes 1 --settle-seconds 0.2 --no-cpu-baseline --selfplay-seconds 0 --agreement-plies 0 --no-f32 --no-bf16 --no-f16 --no-smi --steps 100 --warmup 10"
 one() {  # label, lib variant, env assignment, bench args...
   label=$1; v=$2; envs=$3; shift 3
   lib=cattus_amd/libcattus_hip${v:+_$v}.so

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Collect the round's measured evidence on a GPU box (run from the repository root):
 #   bash scripts/collect_profiles.sh [TAG]
-# Writes gpurun_out/<TAG>/: the default bench line, rocprofv3 kernel stats of the same command per dtype, and the
+# Writes $OUT (below): the --full bench line, rocprofv3 kernel stats of the headline steps per dtype, and the
 # separate PMC passes (HBM-side traffic, MFMA busy) per dtype.  scripts/summarise_pmc.py turns the PMC CSVs into JSON,
 # scripts/make_traffic_json.py into the file bench.py reads for roofline.traffic.
 set -u
@@ -13,7 +13,7 @@ QUIET="--lanes 1 --settle-seconds 0 --no-cpu-baseline --selfplay-seconds 0 --agr
 # PARTS (default "bench dtypes workloads") selects what runs: one gpurun call holds 20 minutes, the whole collection takes more
 PARTS=${PARTS:-bench dtypes workloads}
 if [[ " $PARTS " == *" bench "* ]]; then
-echo "== bench (defaults)"; timeout -k 10 900 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
+echo "== bench --full"; timeout -k 10 900 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
 tail -c 400 "$OUT/bench.json"; echo
 fi
 if [[ " $PARTS " == *" dtypes "* ]]; then
@@ -37,7 +37,7 @@ fi
 if [[ " $PARTS " == *" workloads "* ]]; then
 for wl in hex7_6x64 chess40x384; do
   echo "== bench --workload $wl"
-  timeout -k 10 600 python3 bench.py --workload $wl --steps 100 --warmup 10 --no-cpu-baseline --no-f32 > "$OUT/bench_$wl.json" 2> "$OUT/bench_$wl.err" || exit 1
+  timeout -k 10 600 python3 bench.py --full --workload $wl --steps 100 --warmup 10 --no-cpu-baseline --no-f32 > "$OUT/bench_$wl.json" 2> "$OUT/bench_$wl.err" || exit 1
   for dt in f16x2 bf16; do
     timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_${wl}_$dt" -o bench -- python3 bench.py --workload $wl --dtype $dt --steps 50 --warmup 5 $QUIET > "$OUT/stats_bench_${wl}_$dt.json" 2> "$OUT/stats_${wl}_$dt.err" || exit 1
     find "$OUT/stats_${wl}_$dt" -name '*kernel_stats.csv' -exec cp {} "$OUT/bench_${wl}_${dt}_kernel_stats.csv" \;

@@ -1,6 +1,6 @@
-"""bench.py's output contract: stdout is exactly ONE line, a JSON object with the driver's keys plus `roofline` and
-`cpu_baseline`; everything else (RCCL's version banner included -- the config-4 leg brings a communicator up even on one
-rank) goes to stderr."""
+"""bench.py's output contract: stdout is exactly ONE line, a JSON object with the driver's keys (with --full also `roofline` and
+`cpu_baseline`); everything else (RCCL's version banner included -- the config-4 leg of --full brings a communicator up even on
+one rank) goes to stderr.  A plain run times the headline and nothing else, and --dump-outputs writes what its last step computed."""
 
 import json
 import subprocess
@@ -14,7 +14,7 @@ ROOT = Path(__file__).resolve().parent.parent
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_on_stdout():
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "6", "--warmup", "2", "--settle-seconds", "0", "--selfplay-seconds", "3",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "6", "--warmup", "2", "--settle-seconds", "0", "--selfplay-seconds", "3",
            "--agreement-plies", "0", "--no-bf16", "--no-f16", "--no-f32", "--lanes", "1"]
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -36,6 +36,35 @@ def test_bench_prints_one_json_line_on_stdout():
 
 
 @pytest.mark.gpu
+def test_plain_bench_times_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """A plain run: the headline keys, none of --full's measurements, and DIR/policy.npy, DIR/value.npy equal to what the
+    blocking entry point computes for the same seeded leaves on an evaluator built as the timed one (same kernels, same bits)."""
+    import numpy as np
+
+    import bench
+    from cattus_amd.evaluator import HipEvaluator
+
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--settle-seconds", "0", "--dump-outputs", str(tmp_path)]
+    p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, p.stdout[:2000]
+    out = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in out, key
+    assert out["steps"] == 3 and out["dtype"] == "f16x2" and out["higher_is_better"] is True
+    assert abs(out["value"] - 256 / (out["ms_per_step"] * 1e-3)) / out["value"] < 1e-6
+    for key in ("roofline", "two_batches_in_flight", "bf16", "f16", "f32", "search_agreement", "selfplay", "roofline_plane_pack", "cpu_baseline"):
+        assert key not in out, key
+    policy, value = np.load(tmp_path / "policy.npy"), np.load(tmp_path / "value.npy")
+    d, blob, planes = bench.make_workload("chess20x256")
+    assert policy.dtype == np.float32 and policy.shape == (256, d.moves) and value.dtype == np.float32 and value.shape == (256,)
+    with HipEvaluator(blob, batch_size=256, plane_words=1, dtype="f16x2") as ev:
+        want_p, want_v = ev.eval(planes)
+    assert (policy == want_p).all() and (value == want_v).all()
+
+
+@pytest.mark.gpu
 def test_bench_gpus_2_without_a_launcher_starts_two_ranks():
     """`python bench.py --gpus 2` with no torchrun in front: the parent (which has not touched the GPU) starts two fresh ranks
     and relays rank 0's line.  This box has one GPU, so the rehearsal switch puts both ranks on device 0 and runs the
@@ -45,7 +74,7 @@ def test_bench_gpus_2_without_a_launcher_starts_two_ranks():
     env = dict(os.environ, BENCH_REHEARSAL="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--settle-seconds", "0", "--selfplay-seconds", "2",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "2", "--steps", "6", "--warmup", "2", "--settle-seconds", "0", "--selfplay-seconds", "2",
            "--agreement-plies", "0", "--no-bf16", "--no-f16", "--no-f32", "--lanes", "1", "--no-smi"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
