@@ -39,3 +39,49 @@ def outputs_equal_ref_tol(policy, value, policy_ref, value_ref) -> bool:
 def blob_for(name: str):
     d, seed, z = load_golden(name)
     return d, seeded_blob(d, seed), z
+
+
+def planes_to_f64(planes: np.ndarray, board: int) -> np.ndarray:
+    """uint64 bitboards [n, C, W64] (bit h*S+w of a plane in bit i & 63 of word i >> 6) -> float64 [n, C, S, S] of 0 / 1."""
+    planes = np.asarray(planes, dtype=np.uint64)
+    hw = board * board
+    i = np.arange(hw)
+    bits = (planes[:, :, i >> 6] >> (i & 63).astype(np.uint64)) & np.uint64(1)
+    return bits.astype(np.float64).reshape(len(planes), planes.shape[1], board, board)
+
+
+def forward_f64(desc: NetDesc, tensors: dict, planes: np.ndarray):
+    """The network in float64 on the CPU, built from the raw tensors (the seeded_tensors / pack_tensors input) and not from a
+    blob, so that a packing or BatchNorm-folding error of the blob path cannot cancel out.  Returns (policy, value) as float64."""
+    import torch
+
+    from cattus_amd.torch_model import PolicyValueNet
+
+    net = PolicyValueNet(desc).to(torch.float64)
+    sd = net.state_dict()
+    for k in sd:
+        if k.endswith("num_batches_tracked"):
+            continue
+        sd[k] = torch.from_numpy(np.asarray(tensors[k], dtype=np.float64).reshape(tuple(sd[k].shape)))
+    net.load_state_dict(sd, strict=True)
+    net.eval()
+    with torch.no_grad():
+        p, v = net(torch.from_numpy(planes_to_f64(planes, desc.board)))
+    return p.numpy(), v.numpy().reshape(-1)
+
+
+# the single-term f16 tower (11 significant bits) against the bf16 one (8): its error on the same leaves is at most a quarter
+F16_OVER_BF16_MAX = 0.25
+
+
+def check_f16_against_f64(label, bound, f16_out, bf16_out, f64_out):
+    """The f16 tower's bars on one set of leaves, each a (policy, value) pair: within ``bound`` (max |dlogit|, max |dvalue|) of
+    the float64 network, at most F16_OVER_BF16_MAX of the bf16 tower's error on the same leaves, and the bf16 outputs fail
+    ``bound`` (a bound that passes bf16 would not notice an f16 tower that lost its extra bits).  Prints the errors first."""
+    ep, ev = float(np.abs(f16_out[0] - f64_out[0]).max()), float(np.abs(f16_out[1] - f64_out[1]).max())
+    bp, bv = float(np.abs(bf16_out[0] - f64_out[0]).max()), float(np.abs(bf16_out[1] - f64_out[1]).max())
+    print("%s: f16 vs f64 max |dlogit| %.3g |dvalue| %.3g; bf16 vs f64 %.3g %.3g" % (label, ep, ev, bp, bv))
+    assert np.isfinite(f16_out[0]).all() and np.isfinite(f16_out[1]).all()
+    assert ep <= bound[0] and ev <= bound[1], (label, ep, ev, bound)
+    assert ep <= F16_OVER_BF16_MAX * bp and ev <= F16_OVER_BF16_MAX * bv, (label, ep, ev, bp, bv)
+    assert bp > bound[0] and bv > bound[1], ("the f16 bound passes the bf16 tower", label, bp, bv, bound)

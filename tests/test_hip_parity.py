@@ -8,7 +8,9 @@ Bars (DESIGN.md "Parity"):
     reference network's outputs on every fixture, and as close to the float64 run of the reference network as an
     f32 runtime is (bounds F16X2_* below).
   * dtype bf16: bf16 operands / f32 accumulation; per-fixture bounds in BF16_MEASURED below (2x the measured error).
-  * dtype f16: single-term f16 operands; per-fixture bounds in F16_MEASURED (2x the measured error, a tenth of bf16's).
+  * dtype f16: single-term f16 operands; per-fixture bounds in F16_MEASURED (2x the measured error, a tenth of bf16's); at full
+    size against the float64 network (helpers.forward_f64) within F16_FULL_VS_F64, at most a quarter of bf16's error on the same
+    leaves (every conv tile: test_f16_tower_gpu.py).
   * dtype f16x2 in Winograd form (evaluators of 8x8-board networks with max_batch > 128): the f16x2 bars.
   * per-leaf results never depend on batch size, slot or neighbours (all dtypes, bit-exact).
 """
@@ -20,10 +22,10 @@ import pytest
 
 from cattus_amd import synth
 from cattus_amd.evaluator import CattusHipError, HipEvaluator, planes_to_tensor
-from cattus_amd.weights import CHESS, NetDesc, hex_game, seeded_blob
+from cattus_amd.weights import CHESS, NetDesc, hex_game, seeded_blob, seeded_tensors
 from oracle import oracle
 
-from helpers import blob_for, golden_names, outputs_equal_ref_tol
+from helpers import F16_OVER_BF16_MAX, blob_for, check_f16_against_f64, forward_f64, golden_names, outputs_equal_ref_tol
 
 pytestmark = pytest.mark.gpu
 
@@ -44,6 +46,11 @@ F16_MEASURED = {
     "hex11_1x1": (2.3e-5, 1e-6), "hex11_2x8": (7.2e-5, 1.3e-5), "hex4_7x16": (2.3e-4, 5.0e-5), "hex7_6x64": (3.7e-4, 5.6e-5),
     "ttt_1x1": (1e-6, 1e-6), "ttt_2x64": (1.4e-4, 8.4e-5), "ttt_5x8": (2.3e-4, 5.4e-5), "chess_4x128": (4.0e-4, 6.0e-5),
 }
+# the single-term f16 tower at full size (max |dlogit|, max |dvalue|): against the float64 network on every leaf of the 256-leaf
+# batch (20x256) and on 64 of the 512 (40x384), and against the f32 tower on all 512; 2x the error measured on an MI355X:
+# 9.43e-4 / 2.94e-4 (bf16 on the same leaves 8.42e-3 / 2.14e-3), 2.69e-3 / 4.60e-4 (bf16 2.55e-2 / 5.23e-3), 2.89e-3 / 6.14e-4
+F16_FULL_VS_F64 = {"20x256": (1.9e-3, 5.9e-4), "40x384": (5.4e-3, 9.2e-4)}
+F16_FULL_VS_F32 = {"40x384": (5.8e-3, 1.23e-3)}
 # split precision against the float64 run of the reference network: measured max |dlogit| 7.4e-7, |dvalue| 2.1e-7 (chess
 # 20x256; the bit-exact f32 tower: 7.7e-7 / 1.9e-7, the reference's own f32 run: 3.3e-7 / 4.9e-8)
 F16X2_POLICY_ATOL_VS_F64, F16X2_VALUE_ATOL_VS_F64 = 1.5e-6, 5e-7
@@ -344,6 +351,8 @@ def test_resident_split_tower_workgroup_shapes_agree_from_512_boards_up():
             assert ev.stats()["saturated"] == 0
 
 
+# f16x2 and f16 are not here: their stems always expand the planes themselves (no separate plane pack exists for them, and the
+# evaluator ignores CATTUS_FUSED_STEM=0), so the switch has nothing to compare
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 @pytest.mark.parametrize("name", ["chess_20x256", "hex11_2x8"])
 def test_fused_stem_equals_separate_plane_pack(name, dtype, monkeypatch):
@@ -362,7 +371,7 @@ def test_fused_stem_equals_separate_plane_pack(name, dtype, monkeypatch):
     assert (got_p == want_p).all() and (got_v == want_v).all()
 
 
-@pytest.mark.parametrize("dtype", ["f32", "bf16", "f16x2"])
+@pytest.mark.parametrize("dtype", ["f32", "bf16", "f16x2", "f16"])
 @pytest.mark.parametrize("game,desc,words,n", [
     ("chess", dict(**CHESS, blocks=3, filters=256, vhc=8, phc=8), 1, 70),
     ("hex11", dict(**hex_game(11), blocks=2, filters=128, vhc=16, phc=16), 2, 21),
@@ -395,7 +404,7 @@ def test_half_cout_workgroups_equal_full_ones(game, desc, words, n, dtype, monke
     ("hex11", dict(**hex_game(11), blocks=2, filters=128, vhc=16, phc=16), 2, 21),   # 128-slot boards: one board per workgroup
     ("ttt", dict(planes=3, board=3, moves=9, blocks=2, filters=64, vhc=8, phc=8), 1, 7),
 ])
-@pytest.mark.parametrize("dtype", ["f16x2", "f32", "bf16"])
+@pytest.mark.parametrize("dtype", ["f16x2", "f32", "bf16", "f16"])
 def test_half_row_workgroups_equal_full_ones(game, desc, words, n, dtype, monkeypatch):
     """Batches that would leave half of the CUs empty run the conv layers on 128-row x 32-cout workgroups (32 pixels per
     consumer wave); CATTUS_CONV_PBW=2 keeps the 256-row ones, =1 forces the small ones wherever the tile is 32 couts: same
@@ -436,7 +445,7 @@ def test_wide_heads_take_the_generic_path_and_refuse_bf16():
     assert ei.value.status == -2
 
 
-@pytest.mark.parametrize("dtype", ["f32", "bf16", "f16x2"])
+@pytest.mark.parametrize("dtype", ["f32", "bf16", "f16x2", "f16"])
 def test_rows_independent_of_batch_composition(dtype):
     d = NetDesc(**CHESS, blocks=3, filters=64, vhc=8, phc=8)
     blob = seeded_blob(d, 77)
@@ -477,7 +486,7 @@ def test_non_finite_logits_are_scrubbed():
     blob = pack_tensors(d, t)
     planes = synth.random_hex_planes(3, 4, 9)
     want_p, want_v = oracle.OracleNet(blob).forward(planes)
-    for dtype in ("f32", "bf16", "f16x2"):
+    for dtype in ("f32", "bf16", "f16x2", "f16"):
         with HipEvaluator(blob, batch_size=4, plane_words=2, dtype=dtype) as ev:
             p, v = ev.eval(planes)
         fmin = np.finfo(np.float32).min
@@ -486,7 +495,7 @@ def test_non_finite_logits_are_scrubbed():
     assert (want_p[:, 3] == fmin).all() and (want_p[:, 7] == fmin).all()
 
 
-@pytest.mark.parametrize("dtype", ["f32", "bf16", "f16x2"])
+@pytest.mark.parametrize("dtype", ["f32", "bf16", "f16x2", "f16"])
 def test_leaf_server_matches_blocking_eval(dtype):
     d = NetDesc(**hex_game(7), blocks=2, filters=64, vhc=16, phc=16)
     blob = seeded_blob(d, 3)
@@ -525,7 +534,8 @@ def test_leaf_server_matches_blocking_eval(dtype):
 def test_full_size_chess_20x256_batch_256():
     """BASELINE config 3 at full size: f32 is bit-exact against the oracle on a sample of the rows;
     all 256 rows are checked through size-independent properties (permutation equivariance,
-    ragged-batch agreement) in both dtypes; bf16 stays within its tolerance of f32 on every row."""
+    ragged-batch agreement) in every dtype; bf16 stays within its tolerance of f32 on every row; f16 (the timed
+    batch's CB=2 tile) within its bound of the float64 network on every row."""
     d = NetDesc(**CHESS, blocks=20, filters=256, vhc=8, phc=8)
     blob = seeded_blob(d, 2)
     planes = synth.random_chess_planes(256, 2)
@@ -561,9 +571,24 @@ def test_full_size_chess_20x256_batch_256():
     # greedy move agreement between the two dtypes (reported, loosely bounded)
     agree = (p16.argmax(1) == p32.argmax(1)).mean()
     assert agree >= 0.9, agree
+    # the single-term f16 tower: the timed batch runs the CB=2 tile, a 100-leaf sub-batch CB=1 PBW=2 and a 37-leaf one CB=1 PBW=1
+    # (tests/test_f16_tower_gpu.py) -- the same bits for every leaf; all 256 leaves against the float64 network, beside bf16
+    with HipEvaluator(blob, batch_size=256, plane_words=1, dtype="f16") as ev:
+        ph, vh = ev.eval(planes)
+        pp, vp = ev.eval(planes[perm])
+        assert (pp == ph[perm]).all() and (vp == vh[perm]).all()
+        for lo, hi in ((0, 255), (100, 200), (3, 40)):
+            pr, vr = ev.eval(planes[lo:hi])
+            assert (pr == ph[lo:hi]).all() and (vr == vh[lo:hi]).all(), (lo, hi)
+        assert ev.stats()["saturated"] == 0
+    p64, v64 = forward_f64(d, seeded_tensors(d, 2), planes)
+    print("chess 20x256, 256 leaves: f16 vs f32 max |dlogit| %.3g |dvalue| %.3g, greedy agreement %.4f" % (
+        np.abs(ph - p32).max(), np.abs(vh - v32).max(), (ph.argmax(1) == p32.argmax(1)).mean()))
+    check_f16_against_f64("chess 20x256, 256 leaves", F16_FULL_VS_F64["20x256"], (ph, vh), (p16, v16), (p64, v64))
+    assert (ph.argmax(1) == p32.argmax(1)).mean() >= 0.99  # greedy move of the f32 tower: measured 256 of 256
 
 
-@pytest.mark.parametrize("dtype", ["f32", "bf16", "f16x2"])
+@pytest.mark.parametrize("dtype", ["f32", "bf16", "f16x2", "f16"])
 def test_eval_legal_softmax_bit_exact_vs_restatement(dtype):
     """cattus_hip_eval_legal = cattus_hip_eval + calc_moves_probs (net/mod.rs:100-119) on the device:
     bit-exact against the oracle's restatement applied to the same evaluator's logits, within 1e-6 of
@@ -618,7 +643,8 @@ def test_eval_legal_scrubbed_logits_get_zero_probability():
 def test_full_size_chess_40x384_batch_512():
     """BASELINE config 5 at full size (107 M parameters, 13.6 GFLOP per leaf, batch 512): f32 bit-exact against
     the oracle on a few rows; every row through size-independent properties (permutation equivariance, ragged
-    sub-batch agreement); bf16 within its stated tolerance of f32 on every row."""
+    sub-batch agreement); bf16 within its stated tolerance of f32 on every row; f16 within its bound of f32 on every
+    row and of the float64 network on a sample of 64."""
     d = NetDesc(**CHESS, blocks=40, filters=384, vhc=8, phc=8)
     blob = seeded_blob(d, 5)
     planes = synth.random_chess_planes(512, 5)
@@ -649,6 +675,21 @@ def test_full_size_chess_40x384_batch_512():
     # 9.9e-7 against the bit-exact f32 tower): bounded at twice that; the reference's own bar is stated for nets of <= 7 blocks
     assert np.abs(ps - p32).max() <= 1.2e-5 and np.abs(vs - v32).max() <= 2e-6, (np.abs(ps - p32).max(), np.abs(vs - v32).max())
     assert (ps.argmax(1) == p32.argmax(1)).all()
+    # the single-term f16 tower: CB=2 on the full batch and on 257 leaves, CB=1 PBW=1 on 20; every row against the f32 tower at
+    # most a quarter of bf16's distance, a sample of 64 rows against the float64 network
+    with HipEvaluator(blob, batch_size=512, plane_words=1, dtype="f16") as ev:
+        ph, vh = ev.eval(planes)
+        for lo, hi in ((100, 357), (40, 60)):
+            pr, vr = ev.eval(planes[lo:hi])
+            assert (pr == ph[lo:hi]).all() and (vr == vh[lo:hi]).all(), (lo, hi)
+        assert ev.stats()["saturated"] == 0
+    dp, dv = float(np.abs(ph - p32).max()), float(np.abs(vh - v32).max())
+    print("chess 40x384, 512 leaves: f16 vs f32 max |dlogit| %.3g |dvalue| %.3g" % (dp, dv))
+    assert dp <= F16_FULL_VS_F32["40x384"][0] and dv <= F16_FULL_VS_F32["40x384"][1], (dp, dv)
+    assert dp <= F16_OVER_BF16_MAX * np.abs(p16 - p32).max() and dv <= F16_OVER_BF16_MAX * np.abs(v16 - v32).max()
+    rows = np.arange(0, 512, 8)
+    p64, v64 = forward_f64(d, seeded_tensors(d, 5), planes[rows])
+    check_f16_against_f64("chess 40x384, 64 of 512 leaves", F16_FULL_VS_F64["40x384"], (ph[rows], vh[rows]), (p16[rows], v16[rows]), (p64, v64))
 
 
 def test_device_pointer_entry_points_and_lanes_agree_with_host_entry_point():
