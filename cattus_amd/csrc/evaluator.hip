@@ -5,6 +5,7 @@
 // There is deliberately no CPU fallback: without a usable HIP device every entry point fails.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -101,6 +102,40 @@ Folded fold_conv(const float* w, uint32_t cout, uint32_t cin, uint32_t taps, con
                 f.w[((size_t)t * cout + co) * cin + ci] = w[((size_t)co * cin + ci) * taps + t] * scale;
     }
     return f;
+}
+
+// The f16 towers' stream shift t >= 0.  An f16x2 epilogue splits an activation y unscaled into hi = f16(y), lo = f16(y - hi): once
+// |y| < 2^-3 lo is an f16 subnormal and y keeps an absolute resolution of 2^-25 instead of 22 significant bits.  Weights get a
+// power-of-two scale per output channel; the residual stream (the stem output, each block's output) is scaled by the trained
+// BatchNorm gamma / beta of the stem and the blocks' _bn2 alone (_bn1 has no affine parameters: the middle activation is unit
+// scale).  So the tower carries the stream at 2^t times its size: stem w, b x 2^t, every block's conv1 w x 2^-t, conv2 w, b x 2^t,
+// the head convs' w x 2^-t -- exact power-of-two products that the per-channel weight scales absorb, the same function in exact
+// arithmetic.  S = median over channels of sqrt(gamma_stem^2 + beta_stem^2 + sum over blocks (gamma_2^2 + beta_2^2)) estimates the
+// stream's RMS.  S >= 1/2 keeps t = 0: the weights, and so the bits, of a tower without the shift (every seeded network: S lies in
+// [0.9, 2.7), near 1 where the blocks are few).  A smaller S is lifted into [1, 2): t = -floor(log2 S), at most 16; 0 where S is 0
+// or not finite.
+int choose_stream_shift(const cattus_net_desc& d, const float* p) {
+    const uint32_t F = d.filters;
+    const float* g0 = p + (size_t)F * d.planes * 9;
+    const float* b0 = g0 + F;
+    const size_t stem = (size_t)F * d.planes * 9 + 4 * F, block = (size_t)2 * F * F * 9 + 6 * F;
+    std::vector<double> s(F);
+    for (uint32_t c = 0; c < F; c++) s[c] = (double)g0[c] * g0[c] + (double)b0[c] * b0[c];
+    for (uint32_t i = 0; i < d.blocks; i++) {
+        const float* g2 = p + stem + i * block + (size_t)F * F * 9 + 2 * F + (size_t)F * F * 9;
+        const float* b2 = g2 + F;
+        for (uint32_t c = 0; c < F; c++) s[c] += (double)g2[c] * g2[c] + (double)b2[c] * b2[c];
+    }
+    std::sort(s.begin(), s.end());
+    const double S = std::sqrt(F % 2 ? s[F / 2] : 0.5 * (s[F / 2 - 1] + s[F / 2]));
+    if (!(S > 0.0) || !std::isfinite(S) || S >= 0.5) return 0;
+    return std::min(16, -ilogb(S));
+}
+
+// w x 2^sw, b x 2^sb (exact: powers of two)
+void shift_folded(Folded& f, int sw, int sb) {
+    for (float& x : f.w) x = ldexpf(x, sw);
+    for (float& x : f.b) x = ldexpf(x, sb);
 }
 
 // One device allocation that a tower's hot buffers are carved from (the Winograd tower: the transformed weights of all layers and
@@ -304,6 +339,9 @@ struct cattus_eval {
     uint32_t cus = 0;
     bool wino_inplace = true;      // CATTUS_WINO_INPLACE=0: a third activation buffer for the blocks' outputs (A/B runs)
     bool split_wfrag = true;       // CATTUS_SPLIT_W=0: f16x2 weights through the LDS ring (conv3x3_split_kernel) instead of the register ring
+    // the f16 towers carry the residual stream at 2^stream_shift times its size (choose_stream_shift); CATTUS_STREAM_SHIFT=0: never
+    bool stream_shift_on = true;
+    int stream_shift = 0;
     // tile-forcing switches (CATTUS_CONV_CB, CATTUS_CONV_PBW: A/B runs, the tile-equality tests) and the f16 towers' saturation
     // counter: this evaluator's own -- a second evaluator in the process (model1 vs model2) neither re-tiles nor shares them
     ConvOpts conv_opts;
@@ -575,11 +613,14 @@ int build(cattus_eval* e, const float* p) {
         return r;
     };
     int rc;
+    const int t = e->stream_shift = act_f16_family(e->act) && e->stream_shift_on ? choose_stream_shift(d, p) : 0;
     {
         const float* w = take((size_t)F * d.planes * 9);
         const float *g = take(F), *be = take(F), *mu = take(F), *var = take(F);
         const uint32_t kc = e->tuned ? (uint32_t)act_kc(e->act) : 1;
-        if ((rc = upload_conv(e, e->stem, fold_conv(w, F, d.planes, 9, g, be, mu, var), F, d.planes, FP, (d.planes + kc - 1) / kc * kc))) return rc;
+        Folded f = fold_conv(w, F, d.planes, 9, g, be, mu, var);
+        if (t) shift_folded(f, t, t);
+        if ((rc = upload_conv(e, e->stem, f, F, d.planes, FP, (d.planes + kc - 1) / kc * kc))) return rc;
         e->cpad0 = e->stem.cin;
     }
     for (uint32_t i = 0; i < d.blocks; i++) {
@@ -587,10 +628,14 @@ int build(cattus_eval* e, const float* p) {
         e->c2.emplace_back(new ConvLayer);
         const float* w1 = take((size_t)F * F * 9);
         const float *mu1 = take(F), *var1 = take(F);
-        if ((rc = upload_conv(e, *e->c1.back(), fold_conv(w1, F, F, 9, nullptr, nullptr, mu1, var1), F, F, FP, FP))) return rc;
+        Folded f1 = fold_conv(w1, F, F, 9, nullptr, nullptr, mu1, var1);
+        if (t) shift_folded(f1, -t, 0);
+        if ((rc = upload_conv(e, *e->c1.back(), f1, F, F, FP, FP))) return rc;
         const float* w2 = take((size_t)F * F * 9);
         const float *g2 = take(F), *be2 = take(F), *mu2 = take(F), *var2 = take(F);
-        if ((rc = upload_conv(e, *e->c2.back(), fold_conv(w2, F, F, 9, g2, be2, mu2, var2), F, F, FP, FP))) return rc;
+        Folded f2 = fold_conv(w2, F, F, 9, g2, be2, mu2, var2);
+        if (t) shift_folded(f2, t, t);
+        if ((rc = upload_conv(e, *e->c2.back(), f2, F, F, FP, FP))) return rc;
     }
     // heads: value rows first, then policy rows, in one [vhc+phc][F] 1x1 conv
     std::vector<float> hw_w((size_t)(d.vhc + d.phc) * F), hw_b(std::max(32u, d.vhc + d.phc), 0.0f);  // bias padded to one 32-row tile
@@ -606,6 +651,7 @@ int build(cattus_eval* e, const float* p) {
     Folded fp = fold_conv(pw, d.phc, F, 1, nullptr, nullptr, pmu, pvar);
     const float* pfc_w = take((size_t)d.moves * d.phc * hw);
     const float* pfc_b = take(d.moves);
+    if (t) shift_folded(fv, -t, 0), shift_folded(fp, -t, 0);  // f32 rows on every path that runs an f16 tower (head_act)
     memcpy(hw_w.data(), fv.w.data(), fv.w.size() * 4);
     memcpy(hw_w.data() + fv.w.size(), fp.w.data(), fp.w.size() * 4);
     memcpy(hw_b.data(), fv.b.data(), fv.b.size() * 4);
@@ -1056,6 +1102,8 @@ CATTUS_API const char* cattus_hip_tower_kernel(const cattus_eval* e) {
     return "conv3x3_mfma_v2_kernel";
 }
 
+CATTUS_API int cattus_hip_stream_shift(const cattus_eval* e) { return e ? e->stream_shift : 0; }
+
 namespace {
 
 // Diagnostic switches of cattus_hip_create_diag (include/cattus_hip_diag.h): "KEY=VALUE;KEY=VALUE".  cattus_hip_create passes none,
@@ -1066,7 +1114,7 @@ struct Switches {
         if (!text) return CATTUS_OK;
         static const char* const known[] = {"CATTUS_CONV_CB", "CATTUS_CONV_PBW", "CATTUS_FUSED_STEM", "CATTUS_T64_CH", "CATTUS_T64_LS", "CATTUS_SPLIT_W",
                                             "CATTUS_T64S_HEADS", "CATTUS_T64S_SHAPE", "CATTUS_TOWER64", "CATTUS_FORCE_GENERIC", "CATTUS_WINO_INPLACE",
-                                            "CATTUS_ARENA", "CATTUS_WINO_KERNEL", "CATTUS_WINO_PERSIST", "CATTUS_WINO_SPIN"};
+                                            "CATTUS_ARENA", "CATTUS_WINO_KERNEL", "CATTUS_WINO_PERSIST", "CATTUS_WINO_SPIN", "CATTUS_STREAM_SHIFT"};
         const std::string s(text);
         size_t at = 0;
         while (at < s.size()) {
@@ -1160,6 +1208,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
     const char* t64s_heads_env = sw.get("CATTUS_T64S_HEADS");
     const char* t64s_d_env = sw.get("CATTUS_T64S_SHAPE");
     const char* tower64_env = sw.get("CATTUS_TOWER64");
+    const char* stream_shift_env = sw.get("CATTUS_STREAM_SHIFT");
 
     std::unique_ptr<cattus_eval> e(new (std::nothrow) cattus_eval);
     if (!e) return fail(CATTUS_E_NOMEM, "out of memory");
@@ -1172,6 +1221,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
     e->t64_force_ch = t64_ch_env ? atoi(t64_ch_env) : 0;
     e->t64_layer_steps = !(t64_ls_env && atoi(t64_ls_env) == 0);
     e->split_wfrag = !(split_w_env && split_w_env[0] == '0');
+    e->stream_shift_on = !(stream_shift_env && stream_shift_env[0] == '0');
     // the tower's form is part of the configuration (a leaf's bits must not depend on the batch it came in, so never per batch):
     // AUTO = Winograd for max_batch > 128 where the shape allows it; WINOGRAD on a shape it does not cover is refused below
     e->winograd = cfg->tower_form == CATTUS_TOWER_WINOGRAD || (cfg->tower_form == CATTUS_TOWER_AUTO && cfg->max_batch > 128);

@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "cattus_hip_runtime_note",
     "cattus_hip_tower_kernel",
     "cattus_hip_create_diag",  # include/cattus_hip_diag.h
+    "cattus_hip_stream_shift",  # include/cattus_hip_diag.h
 ]
 
 
@@ -79,7 +80,7 @@ TOWER_FORMS = {"auto": 0, "direct": 1, "winograd": 2}  # cattus_tower_form
 # `CATTUS_TOWER64=0 python scripts/...` and monkeypatch.setenv keep working.  CATTUS_WINOGRAD=0/1 (rounds 3-4) maps to tower_form.
 DIAG_SWITCHES = ("CATTUS_CONV_CB", "CATTUS_CONV_PBW", "CATTUS_FUSED_STEM", "CATTUS_T64_CH", "CATTUS_T64_LS", "CATTUS_SPLIT_W", "CATTUS_T64S_HEADS",
                  "CATTUS_T64S_SHAPE", "CATTUS_TOWER64", "CATTUS_FORCE_GENERIC", "CATTUS_WINO_INPLACE", "CATTUS_ARENA", "CATTUS_WINO_KERNEL",
-                 "CATTUS_WINO_PERSIST", "CATTUS_WINO_SPIN")
+                 "CATTUS_WINO_PERSIST", "CATTUS_WINO_SPIN", "CATTUS_STREAM_SHIFT")
 
 
 class Stats(C.Structure):
@@ -142,6 +143,7 @@ def load_library():
     L.cattus_hip_runtime_note.restype = C.c_char_p
     L.cattus_hip_tower_kernel.argtypes = [vp]
     L.cattus_hip_tower_kernel.restype = C.c_char_p
+    L.cattus_hip_stream_shift.argtypes = [vp]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("cattus_hip_last_error", "cattus_hip_version", "cattus_hip_runtime_note", "cattus_hip_host_alloc",
@@ -316,6 +318,10 @@ class HipEvaluator:
     def tower_kernel(self) -> str:
         """Name of the kernel that runs this evaluator's tower."""
         return self._lib.cattus_hip_tower_kernel(self._h).decode()
+
+    def stream_shift(self) -> int:
+        """t: the f16 towers carry the residual stream at 2^t times its size (0 for f32 and bf16; include/cattus_hip_diag.h)."""
+        return self._lib.cattus_hip_stream_shift(self._h)
 
     def mfma_sustained(self, seconds: float = 1.0) -> float:
         """TFLOP/s the device's matrix pipe sustains on back-to-back MFMAs of this evaluator's tower kind (diagnostic)."""

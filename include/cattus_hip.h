@@ -93,7 +93,8 @@ typedef struct cattus_net_desc {
 /* Model::new (model.rs:61): parse the weight blob (copied), fold BatchNorm, upload.  Everything that selects a code path is in
  * `cfg`; the library reads two operational environment variables and no other: CATTUS_HIP_WAIT=block (the host thread sleeps
  * on an event instead of spinning while a batch runs) and CATTUS_ROCTX=1 (ROCTx ranges around every batch).  The A/B switches
- * of the tests and timing scripts go through cattus_hip_create_diag (cattus_hip_diag.h), never through the environment. */
+ * of the tests and timing scripts go through cattus_hip_create_diag (cattus_hip_diag.h), never through the environment; the
+ * same header declares cattus_hip_stream_shift(), what an f16 / f16x2 evaluator chose for its residual stream. */
 int cattus_hip_create(const void* weights, size_t nbytes, const cattus_eval_config* cfg, cattus_eval** out);
 void cattus_hip_destroy(cattus_eval* e);
 int cattus_hip_desc(const cattus_eval* e, cattus_net_desc* out);

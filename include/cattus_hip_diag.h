@@ -26,8 +26,16 @@ extern "C" {
  *   CATTUS_WINO_PERSIST=0   the Winograd tower as per-layer launches instead of one launch (tower_wino4_kernel); CATTUS_WINO_SPIN=<n>:
  *                           polls a hand-off wait of that launch may take before it gives up (a launch that gave up is run again,
  *                           per layer: the tests set 1 to walk that path)
- *   CATTUS_WINO_INPLACE=0, CATTUS_ARENA=0     memory plan of the Winograd tower (a third activation buffer; separate allocations) */
+ *   CATTUS_WINO_INPLACE=0, CATTUS_ARENA=0     memory plan of the Winograd tower (a third activation buffer; separate allocations)
+ * One switch does change what a leaf evaluates to, and exists to show why its default is what it is:
+ *   CATTUS_STREAM_SHIFT=0   the f16 / f16x2 towers carry the residual stream at its own size, however small (see below) */
 int cattus_hip_create_diag(const void* weights, size_t nbytes, const cattus_eval_config* cfg, const char* switches, cattus_eval** out);
+
+/* The stream shift t >= 0 of an f16 / f16x2 evaluator: its tower carries the residual stream at 2^t times its size, so that a
+ * stream the trained BatchNorm parameters make small keeps the split activations' lo halves out of the f16 subnormals (exact
+ * power-of-two weight products, chosen once from the network at create time; evaluator.hip, choose_stream_shift).  0 for f32
+ * and bf16, for a network whose stream is not small, and under CATTUS_STREAM_SHIFT=0. */
+int cattus_hip_stream_shift(const cattus_eval* e);
 
 #ifdef __cplusplus
 }

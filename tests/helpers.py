@@ -7,7 +7,7 @@ from pathlib import Path
 
 import numpy as np
 
-from cattus_amd.weights import NetDesc, seeded_blob
+from cattus_amd.weights import BN_EPS, NetDesc, seeded_blob
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
 
@@ -85,3 +85,32 @@ def check_f16_against_f64(label, bound, f16_out, bf16_out, f64_out):
     assert ep <= bound[0] and ev <= bound[1], (label, ep, ev, bound)
     assert ep <= F16_OVER_BF16_MAX * bp and ev <= F16_OVER_BF16_MAX * bv, (label, ep, ev, bp, bv)
     assert bp > bound[0] and bv > bound[1], ("the f16 bound passes the bf16 tower", label, bp, bv, bound)
+
+
+def stream_twin(desc: NetDesc, tensors: dict, c: float) -> dict:
+    """The tensors of a network that computes the same function as ``tensors`` with its residual stream (the stem output and
+    every block's output) multiplied by ``c``, a power of two: stem BatchNorm and every block's _bn2 gamma, beta x c; every
+    block's _bn1 and the two head BatchNorms (no affine parameters: they read the stream) running_mean x c and running_var ->
+    c^2 (var + eps) - eps.  Computed in float64, returned as float32 (the blob is f32), so the new statistics are rounded: each
+    twin is its own network, to be compared with its own forward_f64.  A variance that comes out <= 0 raises (with the seeded
+    var >= 0.5 this limits c to >= 2^-7)."""
+    c = float(c)
+    if not (c > 0 and math.frexp(c)[0] == 0.5):
+        raise ValueError(f"stream_twin: c = {c} is not a power of two")
+    out = dict(tensors)
+
+    def f64(k):
+        return np.asarray(tensors[k], dtype=np.float64)
+
+    affine = ["_conv1._bn."] + [f"_residual_blocks.{i}._bn2." for i in range(desc.blocks)]
+    for p in affine:
+        out[p + "weight"] = (f64(p + "weight") * c).astype(np.float32)
+        out[p + "bias"] = (f64(p + "bias") * c).astype(np.float32)
+    readers = [f"_residual_blocks.{i}._bn1." for i in range(desc.blocks)] + ["_value_head.0._bn.", "_policy_head.0._bn."]
+    for p in readers:
+        var = c * c * (f64(p + "running_var") + BN_EPS) - BN_EPS
+        if not (var > 0).all():
+            raise ValueError(f"stream_twin: c = {c} gives {p}running_var <= 0")
+        out[p + "running_mean"] = (f64(p + "running_mean") * c).astype(np.float32)
+        out[p + "running_var"] = var.astype(np.float32)
+    return out

@@ -6,7 +6,7 @@ Bars (DESIGN.md "Parity"):
     reference's cross-runtime tolerance of the reference network's own outputs (tests/golden).
   * dtype f16x2 (split precision, the product default): within the reference's cross-runtime tolerance of the
     reference network's outputs on every fixture, and as close to the float64 run of the reference network as an
-    f32 runtime is (bounds F16X2_* below).
+    f32 runtime is (bounds F16X2_* below), at every scale of the residual stream on every f16x2 kernel (test_split_range_gpu.py).
   * dtype bf16: bf16 operands / f32 accumulation; per-fixture bounds in BF16_MEASURED below (2x the measured error).
   * dtype f16: single-term f16 operands; per-fixture bounds in F16_MEASURED (2x the measured error, a tenth of bf16's); at full
     size against the float64 network (helpers.forward_f64) within F16_FULL_VS_F64, at most a quarter of bf16's error on the same
