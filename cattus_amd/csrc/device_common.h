@@ -1,5 +1,6 @@
-// Device-side definitions shared by the kernel translation units (kernels.hip, kernels_t64s.hip): vector types, the MFMA
-// wrappers, the fragment-order index, the split tower's LDS pitch and weight-stage constants, small helpers.
+// Definitions shared by the kernel translation units: vector types, the MFMA wrappers, the fragment-order index, the split
+// tower's LDS pitch and weight-stage constants, small helpers; and, for their host side, what a kernel family's one list of
+// instances is written with.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -104,5 +105,26 @@ constexpr int SP = 144;                                 // LDS row pitch
 constexpr int SW_D = 6;                       // weight stages in flight per consumer wave; divides the 18 stages of a chunk
 constexpr int SW_STAGE = 2048;                // bytes per 32-cout block and stage: hi fragment, lo fragment
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+
+// ---- host side: a kernel family's instances, listed once ----
+// Next to its kernels every templated family has one for_each_* visitor.  It calls f(kernel, ..., template arguments as
+// std::integral_constant values) for every instance that exists; an `if constexpr` on the family's rule keeps the other
+// combinations from being instantiated.  The family's prepare_* sets the dynamic-LDS opt-in through it and its launcher picks,
+// through it, the instance whose arguments equal the launch's run-time key (a scan of at most 18 entries).
+template <class F>
+void each_bool(F&& f) {
+    f(std::false_type{});
+    f(std::true_type{});
+}
+template <int... V, class F>
+void each_int(F&& f) {
+    (f(std::integral_constant<int, V>{}), ...);
+}
+// The opt-in for more than 64 KiB of dynamic LDS is a per-device function attribute; `err` keeps the first failure.
+template <class K>
+void lds_opt_in(hipError_t& err, K* kernel, int bytes) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (err == hipSuccess) err = e;
+}
 
 }  // namespace cattus

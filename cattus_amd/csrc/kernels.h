@@ -105,11 +105,6 @@ bool wino4_supported(uint32_t bpad, uint32_t cin, uint32_t cout, uint32_t S);
 void launch_conv3x3_wino4(const float* in, const void* wu, const float* bias, const float* res, float* out, uint32_t bpad, uint32_t cin,
                           uint32_t cout, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, unsigned* sat);
 hipError_t prepare_wino4();
-// ---- K1w8: the same layer on EIGHT waves of 128 accumulator registers, two per SIMD (kernels_wino8.hip); same arguments, U and bits ----
-bool wino8_supported(uint32_t bpad, uint32_t cin, uint32_t cout, uint32_t S);
-void launch_conv3x3_wino8(const float* in, const void* wu, const float* bias, const float* res, float* out, uint32_t bpad, uint32_t cin,
-                          uint32_t cout, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, unsigned* sat);
-hipError_t prepare_wino8();
 // The whole Winograd tower in one launch (tower_wino4_kernel): a table of its layers in device memory (an even number: residual blocks,
 // the first layer of a block without skip rows, the second with; res may equal out), `ready` = nlayers x (bpad / 4) zeroed counters, `err` a zeroed word the launch sets when a hand-off wait ran out of
 // `spin_budget` polls (the outputs are then invalid: run the batch on the per-layer launches).  Only while wino4_tower_fits: every
@@ -178,7 +173,7 @@ struct Tower64SplitArgs {
 constexpr int T64S_MAX_LAYERS = 81;  // the bias table of all layers lives in LDS (512 B per layer)
 // rows % 256 == 0 (whole boards); one workgroup per board
 // shape (64-slot boards): 1 = one board per workgroup (four one-tile waves), 2 = two boards per workgroup (a wave holds a
-// board's 64 pixels x 32 couts), 9 = shape 1 with a 9-stage weight ring and two stages of pixel look-ahead (A/B); 0 = by grid size
+// board's 64 pixels x 32 couts); anything else = by grid size
 void launch_tower64_split(const Tower64SplitArgs& args, uint32_t rows, int shape, hipStream_t st, hipEvent_t ev_start = nullptr,
                           hipEvent_t ev_stop = nullptr);
 hipError_t prepare_tower64_split();  // its dynamic-LDS opt-in; called by prepare_device()

@@ -1410,177 +1410,99 @@ __global__ void __launch_bounds__(512, 2)
     STAMP_FLUSH(wave);
 }
 
-// Every conv variant that exists, with its opt-in for > 64 KiB of dynamic LDS (a per-device function attribute).
-// Called once per device from cattus_hip_create (under its lock), so that no launch ever races the attribute call.
+// ---- host side of the three per-layer conv kernels: every instance listed once ----
+// A family as a type: the instance <R, BIG, STEM, CB, PBW>, its dynamic LDS bytes, its block size, its element type.
 template <typename T>
-static hipError_t conv_attrs_for() {
-    hipError_t err = hipSuccess;
-    auto set = [&](const void* fn) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, V2_LDS_TOTAL);
-        if (e != hipSuccess && err == hipSuccess) err = e;
-    };
-#define CATTUS_ATTR_CB(CBV)                                                                           \
-    set(reinterpret_cast<const void*>(&conv3x3_mfma_v2_kernel<T, false, false, false, CBV>));         \
-    set(reinterpret_cast<const void*>(&conv3x3_mfma_v2_kernel<T, true, false, false, CBV>));          \
-    set(reinterpret_cast<const void*>(&conv3x3_mfma_v2_kernel<T, false, true, false, CBV>));          \
-    set(reinterpret_cast<const void*>(&conv3x3_mfma_v2_kernel<T, true, true, false, CBV>));           \
-    set(reinterpret_cast<const void*>(&conv3x3_mfma_v2_kernel<T, false, false, true, CBV>));          \
-    set(reinterpret_cast<const void*>(&conv3x3_mfma_v2_kernel<T, false, true, true, CBV>));
-    CATTUS_ATTR_CB(1)
-    CATTUS_ATTR_CB(2)
-#undef CATTUS_ATTR_CB
-    // the 128-row workgroups of the 32-cout tile
-    set(reinterpret_cast<const void*>(&conv3x3_mfma_v2_kernel<T, false, false, false, 1, 1>));
-    set(reinterpret_cast<const void*>(&conv3x3_mfma_v2_kernel<T, true, false, false, 1, 1>));
-    set(reinterpret_cast<const void*>(&conv3x3_mfma_v2_kernel<T, false, true, false, 1, 1>));
-    set(reinterpret_cast<const void*>(&conv3x3_mfma_v2_kernel<T, true, true, false, 1, 1>));
-    set(reinterpret_cast<const void*>(&conv3x3_mfma_v2_kernel<T, false, false, true, 1, 1>));
-    set(reinterpret_cast<const void*>(&conv3x3_mfma_v2_kernel<T, false, true, true, 1, 1>));
-    return err;
+struct ConvV2 {  // conv3x3_mfma_v2_kernel: f32, bf16, single-term f16
+    typedef T elem;
+    static constexpr bool HALF_ROWS = true;
+    static constexpr int THREADS = 256 + 64 * NLOAD;
+    static constexpr int lds(int, int) { return V2_LDS_TOTAL; }
+    template <bool R, bool BIG, bool STEM, int CB, int PBW>
+    static auto kernel() { return &conv3x3_mfma_v2_kernel<T, R, BIG, STEM, CB, PBW>; }
+};
+struct ConvSplit {  // conv3x3_split_kernel (weights through the LDS ring): it has no 128-row workgroup
+    typedef _Float16 elem;
+    static constexpr bool HALF_ROWS = false;
+    static constexpr int THREADS = 512;
+    static constexpr int lds(int, int) { return SP_LDS_TOTAL; }
+    template <bool R, bool BIG, bool STEM, int CB, int PBW>
+    static auto kernel() { return &conv3x3_split_kernel<R, BIG, STEM, CB>; }
+};
+struct ConvSplitW {  // conv3x3_splitw_kernel (weights in a register ring)
+    typedef _Float16 elem;
+    static constexpr bool HALF_ROWS = true;
+    static constexpr int THREADS = 512;
+    static constexpr int lds(int cb, int pbw) { return sw_lds_total(cb, pbw); }  // 53,536 B on the 128-row tile: that one would do without the opt-in
+    template <bool R, bool BIG, bool STEM, int CB, int PBW>
+    static auto kernel() { return &conv3x3_splitw_kernel<R, BIG, STEM, CB, PBW>; }
+};
+
+// Every instance of family K that exists, f(kernel, LDS bytes, R, BIG, STEM, CB, PBW): the stem has no skip rows; the 128-row
+// workgroup (PBW = 1) exists on the 32-cout tile (CB = 1) only, and only where the family has it.  18 per family, 12 without it.
+template <class K, class F>
+static void for_each_conv(F&& f) {
+    each_bool([&](auto r) { each_bool([&](auto big) { each_bool([&](auto stem) { each_int<1, 2>([&](auto cb) { each_int<1, 2>([&](auto pbw) {
+        constexpr bool R = decltype(r)::value, BIG = decltype(big)::value, STEM = decltype(stem)::value;
+        constexpr int CB = decltype(cb)::value, PBW = decltype(pbw)::value;
+        if constexpr (!(R && STEM) && (PBW == 2 || (CB == 1 && K::HALF_ROWS)))
+            f(K::template kernel<R, BIG, STEM, CB, PBW>(), K::lds(CB, PBW), r, big, stem, cb, pbw);
+    }); }); }); }); });
 }
-static hipError_t split_attrs() {
-    hipError_t err = hipSuccess;
-    auto set = [&](const void* fn) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, SP_LDS_TOTAL);
-        if (e != hipSuccess && err == hipSuccess) err = e;
-    };
-#define CATTUS_ATTR_CB(CBV)                                                                  \
-    set(reinterpret_cast<const void*>(&conv3x3_split_kernel<false, false, false, CBV>));     \
-    set(reinterpret_cast<const void*>(&conv3x3_split_kernel<true, false, false, CBV>));      \
-    set(reinterpret_cast<const void*>(&conv3x3_split_kernel<false, true, false, CBV>));      \
-    set(reinterpret_cast<const void*>(&conv3x3_split_kernel<true, true, false, CBV>));       \
-    set(reinterpret_cast<const void*>(&conv3x3_split_kernel<false, false, true, CBV>));      \
-    set(reinterpret_cast<const void*>(&conv3x3_split_kernel<false, true, true, CBV>));
-    CATTUS_ATTR_CB(1)
-    CATTUS_ATTR_CB(2)
-#undef CATTUS_ATTR_CB
-    auto setw = [&](const void* fn, int cb) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, sw_lds_total(cb));
-        if (e != hipSuccess && err == hipSuccess) err = e;
-    };
-#define CATTUS_ATTR_CB(CBV)                                                                        \
-    setw(reinterpret_cast<const void*>(&conv3x3_splitw_kernel<false, false, false, CBV>), CBV);    \
-    setw(reinterpret_cast<const void*>(&conv3x3_splitw_kernel<true, false, false, CBV>), CBV);     \
-    setw(reinterpret_cast<const void*>(&conv3x3_splitw_kernel<false, true, false, CBV>), CBV);     \
-    setw(reinterpret_cast<const void*>(&conv3x3_splitw_kernel<true, true, false, CBV>), CBV);      \
-    setw(reinterpret_cast<const void*>(&conv3x3_splitw_kernel<false, false, true, CBV>), CBV);     \
-    setw(reinterpret_cast<const void*>(&conv3x3_splitw_kernel<false, true, true, CBV>), CBV);
-    CATTUS_ATTR_CB(1)
-    CATTUS_ATTR_CB(2)
-#undef CATTUS_ATTR_CB
-    // the 128-row workgroup needs no opt-in (53,536 B)
-    static_assert(sw_lds_total(1, 1) <= 64 * 1024, "the small tile fits the default dynamic LDS limit");
-    return err;
+
+// Every conv instance's opt-in for its dynamic LDS (a per-device function attribute), from prepare_device().
+template <class K>
+static void conv_opt_in(hipError_t& err) {
+    for_each_conv<K>([&](auto kernel, int lds, auto...) { lds_opt_in(err, kernel, lds); });
+}
+
+// The tile of a layer's launch.  256 rows x 64 couts per workgroup (CB = 2); 256 rows x 32 couts (CB = 1) while that grid would leave
+// half of the CUs empty; 128 rows x 32 couts (PBW = 1) while even the 32-cout grid would, where the kernel has that tile.
+// ConvOpts::cb and ::pbw force either choice (CB = 2 has no 128-row workgroup whatever pbw says).
+struct ConvTile {
+    int cb, pbw;
+    uint32_t grid;
+};
+static ConvTile conv_tile(uint32_t bpad, uint32_t slots, uint32_t cout, const ConvOpts& opts, bool has_half_rows) {
+    const uint32_t full_grid = (bpad * slots / ROWS_PER_WG) * (cout / COUT_PER_WG);
+    int cb = full_grid <= 128 ? 1 : 2;
+    if (opts.cb == 1 || opts.cb == 2) cb = opts.cb;
+    const uint32_t grid = full_grid * (cb == 1 ? 2 : 1);
+    const bool half_rows = has_half_rows && cb == 1 && ((grid <= 128 && opts.pbw != 2) || opts.pbw == 1);
+    return {cb, half_rows ? 1 : 2, half_rows ? grid * 2 : grid};
 }
 
 void launch_conv3x3_mfma(Act act, const void* in, const void* w, const float* bias, const void* res, void* out,
                          uint32_t bpad, uint32_t cin, uint32_t cout, uint32_t S, hipStream_t st, hipEvent_t ev_start,
                          hipEvent_t ev_stop, const StemInput* stem, int flags, const ConvOpts& opts) {
-    const uint32_t slots = tower_slots(S);
-    // 256 rows x 64 couts per workgroup; 256 rows x 32 couts while that grid would leave half of the CUs empty
-    const uint32_t full_grid = (bpad * slots / ROWS_PER_WG) * (cout / COUT_PER_WG);
-    int cb = full_grid <= 128 ? 1 : 2;
-    if (opts.cb == 1 || opts.cb == 2) cb = opts.cb;
-    unsigned* const sat = opts.saturated;
-    if (act_f16_family(act) && !sat) {
+    if (act_f16_family(act) && !opts.saturated) {
         fprintf(stderr, "cattus: launch_conv3x3_mfma: the f16 towers need ConvOpts::saturated\n");
         abort();
     }
-    const dim3 grid(full_grid * (cb == 1 ? 2 : 1));
-    if (act == Act::F16S) {
-        typedef _Float16 H;
-        const bool wfrag = (flags & CONV_W_FRAG) != 0;  // `w` is in fragment order: the register-ring kernel
-        if (wfrag && !stem && cin < 64) {  // its loaders request two chunks up front (kernels.h); the evaluator pads filters to 64
-            fprintf(stderr, "cattus: launch_conv3x3_mfma: CONV_W_FRAG needs cin >= 64 on a non-stem layer (got %u)\n", cin);
-            abort();
-        }
-        // 128 rows x 32 couts per workgroup while even the 32-cout grid would leave half of the CUs empty (register ring only)
-        const int pbw_forced = opts.pbw;
-        const bool half_rows = wfrag && cb == 1 && ((grid.x <= 128 && pbw_forced != 2) || pbw_forced == 1);
-        const dim3 grid_half(grid.x * 2);
-#define CATTUS_LAUNCH_SPLIT(R, BIG, STEMV, CBV, SPV)                                                                                   \
-    do {                                                                                                                               \
-        if (wfrag && half_rows && CBV == 1)                                                                                            \
-            hipExtLaunchKernelGGL((conv3x3_splitw_kernel<R, BIG, STEMV, 1, 1>), grid_half, dim3(512), sw_lds_total(1, 1), st, ev_start, \
-                                  ev_stop, 0, (const H*)in, (const H*)w, bias, (const H*)res, (H*)out, sat, (int)cin, (int)cout, (int)S,   \
-                                  flags, SPV);                                                                                         \
-        else if (wfrag)                                                                                                                \
-            hipExtLaunchKernelGGL((conv3x3_splitw_kernel<R, BIG, STEMV, CBV>), grid, dim3(512), sw_lds_total(CBV), st, ev_start,       \
-                                  ev_stop, 0, (const H*)in, (const H*)w, bias, (const H*)res, (H*)out, sat, (int)cin, (int)cout, (int)S,   \
-                                  flags, SPV);                                                                                         \
-        else                                                                                                                           \
-            hipExtLaunchKernelGGL((conv3x3_split_kernel<R, BIG, STEMV, CBV>), grid, dim3(512), SP_LDS_TOTAL, st, ev_start, ev_stop, 0, \
-                                  (const H*)in, (const H*)w, bias, (const H*)res, (H*)out, sat, (int)cin, (int)cout, (int)S, flags, SPV);   \
-    } while (0)
-#define CATTUS_LAUNCH_SPLIT_CB(CBV)                                                                       \
-    do {                                                                                                  \
-        if (stem) {                                                                                       \
-            const StemPlanes<true> spv{stem->planes, stem->n, stem->C, stem->w64};                        \
-            if (slots == 128) CATTUS_LAUNCH_SPLIT(false, true, true, CBV, spv);                           \
-            else CATTUS_LAUNCH_SPLIT(false, false, true, CBV, spv);                                       \
-        } else if (slots == 128) {                                                                        \
-            if (res) CATTUS_LAUNCH_SPLIT(true, true, false, CBV, StemPlanes<false>{});                    \
-            else CATTUS_LAUNCH_SPLIT(false, true, false, CBV, StemPlanes<false>{});                       \
-        } else {                                                                                          \
-            if (res) CATTUS_LAUNCH_SPLIT(true, false, false, CBV, StemPlanes<false>{});                   \
-            else CATTUS_LAUNCH_SPLIT(false, false, false, CBV, StemPlanes<false>{});                      \
-        }                                                                                                 \
-    } while (0)
-        if (cb == 1) CATTUS_LAUNCH_SPLIT_CB(1);
-        else CATTUS_LAUNCH_SPLIT_CB(2);
-#undef CATTUS_LAUNCH_SPLIT_CB
-#undef CATTUS_LAUNCH_SPLIT
-        return;
+    const bool wfrag = act == Act::F16S && (flags & CONV_W_FRAG) != 0;  // `w` is in fragment order: the register-ring kernel
+    if (wfrag && !stem && cin < 64) {  // its loaders request two chunks up front (kernels.h); the evaluator pads filters to 64
+        fprintf(stderr, "cattus: launch_conv3x3_mfma: CONV_W_FRAG needs cin >= 64 on a non-stem layer (got %u)\n", cin);
+        abort();
     }
-    // 128 rows x 32 couts per workgroup while even the 32-cout grid would leave half of the CUs empty (as the split conv does)
-    const int pbw_forced2 = opts.pbw;
-    const bool half_rows2 = cb == 1 && ((grid.x <= 128 && pbw_forced2 != 2) || pbw_forced2 == 1);
-    const dim3 grid_half2(grid.x * 2);
-#define CATTUS_LAUNCH_CONV2(T, R, BIG, CBV)                                                               \
-    do {                                                                                                  \
-        if (half_rows2 && CBV == 1)                                                                       \
-            hipExtLaunchKernelGGL((conv3x3_mfma_v2_kernel<T, R, BIG, false, 1, 1>), grid_half2, dim3(256 + 64 * NLOAD), V2_LDS_TOTAL, st, ev_start, ev_stop, 0, \
-                                  (const T*)in, (const T*)w, bias, (const T*)res, (T*)out, sat, (int)cin, (int)cout, (int)S, flags, StemPlanes<false>{}); \
-        else                                                                                              \
-            hipExtLaunchKernelGGL((conv3x3_mfma_v2_kernel<T, R, BIG, false, CBV>), grid, dim3(256 + 64 * NLOAD), V2_LDS_TOTAL, st, ev_start, ev_stop, 0, \
-                                  (const T*)in, (const T*)w, bias, (const T*)res, (T*)out, sat, (int)cin, (int)cout, (int)S, flags, StemPlanes<false>{}); \
-    } while (0)
-#define CATTUS_LAUNCH_STEM(T, BIG, CBV)                                                                   \
-    do {                                                                                                  \
-        if (half_rows2 && CBV == 1)                                                                       \
-            hipExtLaunchKernelGGL((conv3x3_mfma_v2_kernel<T, false, BIG, true, 1, 1>), grid_half2, dim3(256 + 64 * NLOAD), V2_LDS_TOTAL, st, ev_start, ev_stop, 0, \
-                                  (const T*)nullptr, (const T*)w, bias, (const T*)nullptr, (T*)out, sat, (int)cin, (int)cout, (int)S, flags, \
-                                  StemPlanes<true>{stem->planes, stem->n, stem->C, stem->w64});           \
-        else                                                                                              \
-            hipExtLaunchKernelGGL((conv3x3_mfma_v2_kernel<T, false, BIG, true, CBV>), grid, dim3(256 + 64 * NLOAD), V2_LDS_TOTAL, st, ev_start, ev_stop, 0, \
-                                  (const T*)nullptr, (const T*)w, bias, (const T*)nullptr, (T*)out, sat, (int)cin, (int)cout, (int)S, flags, \
-                                  StemPlanes<true>{stem->planes, stem->n, stem->C, stem->w64});           \
-    } while (0)
-#define CATTUS_LAUNCH_CONV2_CB(T, CBV)                            \
-    do {                                                          \
-        if (stem) {                                               \
-            if (slots == 128) CATTUS_LAUNCH_STEM(T, true, CBV);   \
-            else CATTUS_LAUNCH_STEM(T, false, CBV);               \
-        } else if (slots == 128) {                                \
-            if (res) CATTUS_LAUNCH_CONV2(T, true, true, CBV);     \
-            else CATTUS_LAUNCH_CONV2(T, false, true, CBV);        \
-        } else {                                                  \
-            if (res) CATTUS_LAUNCH_CONV2(T, true, false, CBV);    \
-            else CATTUS_LAUNCH_CONV2(T, false, false, CBV);       \
-        }                                                         \
-    } while (0)
-#define CATTUS_LAUNCH_CONV2_T(T)                  \
-    do {                                          \
-        if (cb == 1) CATTUS_LAUNCH_CONV2_CB(T, 1); \
-        else CATTUS_LAUNCH_CONV2_CB(T, 2);        \
-    } while (0)
-    if (act == Act::BF16) CATTUS_LAUNCH_CONV2_T(__bf16);
-    else if (act == Act::F16) CATTUS_LAUNCH_CONV2_T(_Float16);
-    else CATTUS_LAUNCH_CONV2_T(float);
-#undef CATTUS_LAUNCH_CONV2_T
-#undef CATTUS_LAUNCH_CONV2_CB
-#undef CATTUS_LAUNCH_STEM
-#undef CATTUS_LAUNCH_CONV2
+    const uint32_t slots = tower_slots(S);
+    const bool has_res = res && !stem;
+    auto launch = [&](auto family) {
+        typedef decltype(family) K;
+        typedef typename K::elem T;
+        const ConvTile tile = conv_tile(bpad, slots, cout, opts, K::HALF_ROWS);
+        for_each_conv<K>([&](auto kernel, int lds, auto r, auto big, auto stemv, auto cb, auto pbw) {
+            if (r != has_res || big != (slots == 128) || stemv != (stem != nullptr) || cb != tile.cb || pbw != tile.pbw) return;
+            StemPlanes<decltype(stemv)::value> sp;
+            if constexpr (decltype(stemv)::value) sp = {stem->planes, stem->n, stem->C, stem->w64};
+            hipExtLaunchKernelGGL(kernel, dim3(tile.grid), dim3(K::THREADS), lds, st, ev_start, ev_stop, 0, (const T*)in, (const T*)w, bias,
+                                  (const T*)res, (T*)out, opts.saturated, (int)cin, (int)cout, (int)S, flags, sp);
+        });
+    };
+    if (wfrag) launch(ConvSplitW{});
+    else if (act == Act::F16S) launch(ConvSplit{});
+    else if (act == Act::BF16) launch(ConvV2<__bf16>{});
+    else if (act == Act::F16) launch(ConvV2<_Float16>{});
+    else launch(ConvV2<float>{});
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2032,51 +1954,41 @@ __global__ void __launch_bounds__(512, 2) tower64_lds_kernel(Tower64Args A) {
     STAMP_FLUSH(wave);
 }
 
-void launch_tower64(const Tower64Args& args, uint32_t rows, int ch, bool layer_steps, hipStream_t st, hipEvent_t ev_start,
-                    hipEvent_t ev_stop) {
-    const bool big = tower_slots(args.S) == 128;
-#define CATTUS_LAUNCH_T64_LS(CH, BIG, LS)                                                                       \
-    hipExtLaunchKernelGGL((tower64_lds_kernel<CH, BIG, LS>), dim3(rows / (256 / CH)), dim3(512), tower64_lds_bytes(CH, LS), st, \
-                          ev_start, ev_stop, 0, args)
-#define CATTUS_LAUNCH_T64(CH, BIG) CATTUS_LAUNCH_T64_LS(CH, BIG, false)
-    if (ch == 4 && !big) {
-        if (layer_steps && args.S * args.S <= 63) CATTUS_LAUNCH_T64_LS(4, false, true);
-        else CATTUS_LAUNCH_T64(4, false);
-    } else {
-        if (big) CATTUS_LAUNCH_T64(2, true);
-        else CATTUS_LAUNCH_T64(2, false);
-    }
-#undef CATTUS_LAUNCH_T64
-#undef CATTUS_LAUNCH_T64_LS
+// Every instance that exists, f(kernel, LDS bytes, CH, BIG, LS): one board per workgroup (CH = 4) on 64-slot boards only, one barrier
+// per layer (LS) with CH = 4 only.
+template <class F>
+static void for_each_tower64(F&& f) {
+    each_int<2, 4>([&](auto ch) { each_bool([&](auto big) { each_bool([&](auto ls) {
+        constexpr int CH = decltype(ch)::value;
+        constexpr bool BIG = decltype(big)::value, LS = decltype(ls)::value;
+        if constexpr (CH == 4 ? !BIG : !LS) f(&tower64_lds_kernel<CH, BIG, LS>, tower64_lds_bytes(CH, LS), ch, big, ls);
+    }); }); });
 }
 
-// The opt-in for > 64 KiB of dynamic LDS is a per-device function attribute.  Every variant gets it here, once per
-// device, before anything is launched on that device: cattus_hip_create calls this under a lock, so two evaluation
-// threads can never meet a variant whose attribute call is still on its way.
+void launch_tower64(const Tower64Args& args, uint32_t rows, int ch, bool layer_steps, hipStream_t st, hipEvent_t ev_start,
+                    hipEvent_t ev_stop) {
+    const bool want_big = tower_slots(args.S) == 128;
+    const int want_ch = ch == 4 && !want_big ? 4 : 2;
+    const bool want_ls = want_ch == 4 && layer_steps && args.S * args.S <= 63;
+    for_each_tower64([&](auto kernel, int lds, auto c, auto big, auto ls) {
+        if (c == want_ch && big == want_big && ls == want_ls)
+            hipExtLaunchKernelGGL(kernel, dim3(rows / (256 / c)), dim3(512), lds, st, ev_start, ev_stop, 0, args);
+    });
+}
+
+// The opt-in for > 64 KiB of dynamic LDS is a per-device function attribute.  Every instance of every family gets it here, once
+// per device, before anything is launched on that device: cattus_hip_create calls this under a lock, so two evaluation
+// threads can never meet an instance whose attribute call is still on its way.  Returns the first error.
 hipError_t prepare_device() {
-    hipError_t err = conv_attrs_for<__bf16>();
-    hipError_t e2 = conv_attrs_for<float>();
-    if (err == hipSuccess) err = e2;
-    e2 = conv_attrs_for<_Float16>();
-    if (err == hipSuccess) err = e2;
-    e2 = split_attrs();
-    if (err == hipSuccess) err = e2;
-    auto set = [&](const void* fn, int bytes) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess && err == hipSuccess) err = e;
-    };
-    set(reinterpret_cast<const void*>(&tower64_lds_kernel<4, false, true>), tower64_lds_bytes(4, true));
-    set(reinterpret_cast<const void*>(&tower64_lds_kernel<4, false, false>), tower64_lds_bytes(4, false));
-    set(reinterpret_cast<const void*>(&tower64_lds_kernel<2, true, false>), tower64_lds_bytes(2, false));
-    set(reinterpret_cast<const void*>(&tower64_lds_kernel<2, false, false>), tower64_lds_bytes(2, false));
-    const hipError_t e3 = prepare_tower64_split();
-    if (err == hipSuccess) err = e3;
-    const hipError_t e4 = prepare_wino();
-    if (err == hipSuccess) err = e4;
-    const hipError_t e5 = prepare_wino4();
-    if (err == hipSuccess) err = e5;
-    const hipError_t e6 = prepare_wino8();
-    if (err == hipSuccess) err = e6;
+    hipError_t err = hipSuccess;
+    conv_opt_in<ConvV2<__bf16>>(err);
+    conv_opt_in<ConvV2<float>>(err);
+    conv_opt_in<ConvV2<_Float16>>(err);
+    conv_opt_in<ConvSplit>(err);
+    conv_opt_in<ConvSplitW>(err);
+    for_each_tower64([&](auto kernel, int lds, auto...) { lds_opt_in(err, kernel, lds); });
+    for (hipError_t e : {prepare_tower64_split(), prepare_wino(), prepare_wino4()})
+        if (err == hipSuccess) err = e;
     return err;
 }
 

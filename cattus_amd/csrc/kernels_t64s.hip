@@ -359,35 +359,33 @@ __global__ void __launch_bounds__(256, 1) tower64_split_kernel(Tower64SplitArgs 
     for (int d = 0; d < D; d++) asm volatile("s_waitcnt vmcnt(0)" : "+v"(ring[d][0]), "+v"(ring[d][1])::"memory");
 }
 
+// Every instance that exists, f(kernel, NPB, BIG), all with six weight stages in flight and one stage of pixel look-ahead: a 128-slot
+// board is one NPB = 2 workgroup.  An instance's dynamic LDS is t64s_lds_bytes(NPB, layers).
+template <class F>
+static void for_each_tower64_split(F&& f) {
+    each_int<1, 2>([&](auto npb) { each_bool([&](auto big) {
+        constexpr int NPB = decltype(npb)::value;
+        constexpr bool BIG = decltype(big)::value;
+        if constexpr (!BIG || NPB == 2) f(&tower64_split_kernel<NPB, 6, 1, BIG>, npb, big);
+    }); });
+}
+
 void launch_tower64_split(const Tower64SplitArgs& args, uint32_t rows, int shape, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    const bool big = tower_slots(args.S) == 128;
-#define CATTUS_LAUNCH_T64S(NPB, D, PA, BIGV)                                                                                      \
-    hipExtLaunchKernelGGL((tower64_split_kernel<NPB, D, PA, BIGV>), dim3(rows / (64 * NPB)), dim3(256),                           \
-                          t64s_lds_bytes(NPB, (int)args.nlayers), st, ev_start, ev_stop, 0, args)
-    if (big) {
-        CATTUS_LAUNCH_T64S(2, 6, 1, true);
-        return;
-    }
+    const bool want_big = tower_slots(args.S) == 128;
     // 64-slot boards: one board per workgroup (measured, hex7 6x64: 47 / 53 / 93 us at 128 / 256 / 512 boards against 72 / 77 / 86
     // with two boards per workgroup, which only pays once every CU holds two of the small workgroups)
-    if (shape == 0) shape = rows / 64 >= 512 && rows % 128 == 0 ? 2 : 1;
+    if (shape != 1 && shape != 2) shape = rows / 64 >= 512 ? 2 : 1;
     if (rows % 128 != 0) shape = 1;
-    if (shape == 2) CATTUS_LAUNCH_T64S(2, 6, 1, false);
-    else if (shape == 9) CATTUS_LAUNCH_T64S(1, 9, 2, false);
-    else CATTUS_LAUNCH_T64S(1, 6, 1, false);
-#undef CATTUS_LAUNCH_T64S
+    const int want_npb = want_big ? 2 : shape;
+    for_each_tower64_split([&](auto kernel, auto npb, auto big) {
+        if (npb == want_npb && big == want_big)
+            hipExtLaunchKernelGGL(kernel, dim3(rows / (64 * npb)), dim3(256), t64s_lds_bytes(npb, (int)args.nlayers), st, ev_start, ev_stop, 0, args);
+    });
 }
 
 hipError_t prepare_tower64_split() {
     hipError_t err = hipSuccess;
-    auto set = [&](const void* fn, int npb) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, t64s_lds_bytes(npb, T64S_MAX_LAYERS));
-        if (e != hipSuccess && err == hipSuccess) err = e;
-    };
-    set(reinterpret_cast<const void*>(&tower64_split_kernel<2, 6, 1, true>), 2);
-    set(reinterpret_cast<const void*>(&tower64_split_kernel<2, 6, 1, false>), 2);
-    set(reinterpret_cast<const void*>(&tower64_split_kernel<1, 6, 1, false>), 1);
-    set(reinterpret_cast<const void*>(&tower64_split_kernel<1, 9, 2, false>), 1);
+    for_each_tower64_split([&](auto kernel, auto npb, auto) { lds_opt_in(err, kernel, t64s_lds_bytes(npb, T64S_MAX_LAYERS)); });
     return err;
 }
 

@@ -368,22 +368,26 @@ bool wino_supported(uint32_t bpad, uint32_t cin, uint32_t cout, uint32_t S) {
     return S == 8 && cin >= 64 && cin % 32 == 0 && cout % 128 == 0 && bpad % 2 == 0;
 }
 
+// Both instances, f(kernel, HAS_RES); either takes WN_LDS_TOTAL bytes of dynamic LDS.
+template <class F>
+static void for_each_wino(F&& f) {
+    each_bool([&](auto r) { f(&conv3x3_wino_kernel<decltype(r)::value>, r); });
+}
+
 void launch_conv3x3_wino(const float* in, const void* wu, const float* bias, const float* res, float* out, uint32_t bpad, uint32_t cin,
                          uint32_t cout, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, unsigned* sat) {
     typedef _Float16 H;
     const dim3 grid((bpad / 2) * (cout / 128));
-    if (res)
-        hipExtLaunchKernelGGL((conv3x3_wino_kernel<true>), grid, dim3(256), WN_LDS_TOTAL, st, ev_start, ev_stop, 0, in, (const H*)wu, bias, res, out,
-                              sat, (int)cin, (int)cout);
-    else
-        hipExtLaunchKernelGGL((conv3x3_wino_kernel<false>), grid, dim3(256), WN_LDS_TOTAL, st, ev_start, ev_stop, 0, in, (const H*)wu, bias, res, out,
-                              sat, (int)cin, (int)cout);
+    for_each_wino([&](auto kernel, auto r) {
+        if (r == (res != nullptr))
+            hipExtLaunchKernelGGL(kernel, grid, dim3(256), WN_LDS_TOTAL, st, ev_start, ev_stop, 0, in, (const H*)wu, bias, res, out, sat, (int)cin, (int)cout);
+    });
 }
 
 hipError_t prepare_wino() {
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, WN_LDS_TOTAL);
-    const hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, WN_LDS_TOTAL);
-    return err != hipSuccess ? err : e2;
+    hipError_t err = hipSuccess;
+    for_each_wino([&](auto kernel, auto) { lds_opt_in(err, kernel, WN_LDS_TOTAL); });
+    return err;
 }
 
 }  // namespace cattus

@@ -608,16 +608,20 @@ bool wino4_supported(uint32_t bpad, uint32_t cin, uint32_t cout, uint32_t S) {
     return S == 8 && cin >= 128 && cin % 32 == 0 && cout >= 128 && cout % 64 == 0 && bpad % 4 == 0;  // 64 filters: the resident tower
 }
 
+// Both instances of the layer kernel, f(kernel, HAS_RES); they and tower_wino4_kernel take W4_LDS_TOTAL bytes of dynamic LDS.
+template <class F>
+static void for_each_wino4(F&& f) {
+    each_bool([&](auto r) { f(&conv3x3_wino4_kernel<decltype(r)::value>, r); });
+}
+
 void launch_conv3x3_wino4(const float* in, const void* wu, const float* bias, const float* res, float* out, uint32_t bpad, uint32_t cin,
                           uint32_t cout, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, unsigned* sat) {
     typedef _Float16 H;
     const dim3 grid((bpad / 4) * (cout / 64));
-    if (res)
-        hipExtLaunchKernelGGL((conv3x3_wino4_kernel<true>), grid, dim3(256), W4_LDS_TOTAL, st, ev_start, ev_stop, 0, in, (const H*)wu, bias, res, out,
-                              sat, (int)cin, (int)cout);
-    else
-        hipExtLaunchKernelGGL((conv3x3_wino4_kernel<false>), grid, dim3(256), W4_LDS_TOTAL, st, ev_start, ev_stop, 0, in, (const H*)wu, bias, res, out,
-                              sat, (int)cin, (int)cout);
+    for_each_wino4([&](auto kernel, auto r) {
+        if (r == (res != nullptr))
+            hipExtLaunchKernelGGL(kernel, grid, dim3(256), W4_LDS_TOTAL, st, ev_start, ev_stop, 0, in, (const H*)wu, bias, res, out, sat, (int)cin, (int)cout);
+    });
 }
 
 // The launch's grid for `tiles` tiles on `cus` CUs: all of them when they fit, else the largest multiple of 8 that does (one workgroup
@@ -643,10 +647,10 @@ extern "C" __attribute__((visibility("default"))) int cattus_hip_debug_stamps_w4
 #endif
 
 hipError_t prepare_wino4() {
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino4_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, W4_LDS_TOTAL);
-    const hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino4_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, W4_LDS_TOTAL);
-    const hipError_t e3 = hipFuncSetAttribute(reinterpret_cast<const void*>(&tower_wino4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, W4_LDS_TOTAL);
-    return err != hipSuccess ? err : e2 != hipSuccess ? e2 : e3;
+    hipError_t err = hipSuccess;
+    for_each_wino4([&](auto kernel, auto) { lds_opt_in(err, kernel, W4_LDS_TOTAL); });
+    lds_opt_in(err, &tower_wino4_kernel, W4_LDS_TOTAL);
+    return err;
 }
 
 }  // namespace cattus

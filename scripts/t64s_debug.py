@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Resident split tower against the per-layer launches, for every ring depth / heads switch and a few batch sizes (GPU box)."""
+"""Resident split tower against the per-layer launches, for every workgroup shape / heads switch and a few batch sizes (GPU box)."""
 import os
 import sys
 
@@ -23,7 +23,7 @@ for n in (128, 300, 600, 1100):
     with HipEvaluator(blob, batch_size=n, plane_words=2, dtype="f16x2") as ev:
         want_p, want_v = ev.eval(planes)
     del os.environ["CATTUS_TOWER64"]
-    for depth in ("1", "2", "9"):
+    for depth in ("1", "2"):
         for heads in ("1", "0"):
             os.environ["CATTUS_T64S_SHAPE"], os.environ["CATTUS_T64S_HEADS"] = depth, heads
             with HipEvaluator(blob, batch_size=n, plane_words=2, dtype="f16x2") as ev:

@@ -330,7 +330,7 @@ def test_resident_tower_row_splits_agree(monkeypatch):
 def test_resident_split_tower_workgroup_shapes_agree_from_512_boards_up():
     """tower64_split_kernel picks its workgroup shape PER LAUNCH from the batch's row count: two boards per workgroup from 512
     boards up, one below (kernels_t64s.hip).  A leaf's bits must not depend on that: an evaluator of 640 boards (hex7 6x64) under
-    every forced shape (CATTUS_T64S_SHAPE=1 / 2 / 9), on a full batch (two-board workgroups by default), a 300-leaf batch (one-board
+    every forced shape (CATTUS_T64S_SHAPE=1 / 2), on a full batch (two-board workgroups by default), a 300-leaf batch (one-board
     workgroups) and a single leaf, against the per-layer launches (CATTUS_TOWER64=0)."""
     d = NetDesc(**hex_game(7), blocks=6, filters=64, vhc=16, phc=16)
     blob = seeded_blob(d, 29)
@@ -339,7 +339,7 @@ def test_resident_split_tower_workgroup_shapes_agree_from_512_boards_up():
     with HipEvaluator(blob, batch_size=n, plane_words=2, dtype="f16x2", switches={"CATTUS_TOWER64": "0"}) as ev:
         assert ev.tower_kernel() == "conv3x3_splitw_kernel"
         want_p, want_v = ev.eval(planes)
-    for shape in (None, "1", "2", "9"):
+    for shape in (None, "1", "2"):
         with HipEvaluator(blob, batch_size=n, plane_words=2, dtype="f16x2", switches={"CATTUS_T64S_SHAPE": shape} if shape else {}) as ev:
             assert ev.tower_kernel() == "tower64_split_kernel"
             got_p, got_v = ev.eval(planes)
@@ -741,7 +741,7 @@ def test_device_pointer_entry_points_and_lanes_agree_with_host_entry_point():
 # 2x2 blocks per wave, the default wherever it covers the shape), k16 = conv3x3_wino_kernel (kernels_wino.hip: 16 frequencies of one block) ----
 WINO_POLICY_ATOL_VS_F64, WINO_VALUE_ATOL_VS_F64 = 1.5e-6, 5e-7  # measured 5.1e-7 / 1.3e-7 (the direct split tower: 6.3e-7 / 2.1e-7)
 # k4 runs as ONE launch (tower_wino4_kernel: the layers chained by hand-off counters) while its grid fits the device, else per layer
-WINO_KERNELS = {"k4": ("tower_wino4_kernel", "conv3x3_wino4_kernel"), "k16": ("conv3x3_wino_kernel",), "k8": ("conv3x3_wino8_kernel",)}
+WINO_KERNELS = {"k4": ("tower_wino4_kernel", "conv3x3_wino4_kernel"), "k16": ("conv3x3_wino_kernel",)}
 
 
 def wino_eval(blob, batch_size, wk, **more):
@@ -787,6 +787,11 @@ def test_winograd_tower_form_is_refused_where_no_kernel_covers_the_shape():
     with pytest.raises(CattusHipError) as ei:
         HipEvaluator(seeded_blob(d, 1), batch_size=16, plane_words=2, dtype="f16x2", tower_form="winograd", switches={})
     assert ei.value.status == -2  # CATTUS_E_UNSUPPORTED
+    # the eight-wave kernel that CATTUS_WINO_KERNEL=k8 once named is gone: the value is refused like any other unknown one
+    d = NetDesc(**CHESS, blocks=2, filters=128, vhc=8, phc=8)
+    with pytest.raises(CattusHipError) as ei:
+        HipEvaluator(seeded_blob(d, 1), batch_size=16, plane_words=1, dtype="f16x2", tower_form="winograd", switches={"CATTUS_WINO_KERNEL": "k8"})
+    assert ei.value.status == -1  # CATTUS_E_INVALID
 
 
 def test_auto_form_follows_max_batch_and_never_the_batch():
@@ -810,7 +815,7 @@ def test_auto_form_follows_max_batch_and_never_the_batch():
 
 @pytest.mark.parametrize("shape", [(3, 128, 256), (2, 192, 200), (2, 256, 24), (1, 384, 512)])
 def test_winograd_kernels_agree_bit_for_bit(shape):
-    """conv3x3_wino4_kernel and conv3x3_wino8_kernel against conv3x3_wino_kernel: per accumulator the same MFMA sequence, V and Y combined in the same order --
+    """conv3x3_wino4_kernel against conv3x3_wino_kernel: per accumulator the same MFMA sequence, V and Y combined in the same order --
     the same bits, on full, ragged and multi-round grids (192 filters: the 4-frequency kernel alone covers them, checked against the
     direct form's tolerance instead)."""
     blocks, filters, n = shape
@@ -823,11 +828,6 @@ def test_winograd_kernels_agree_bit_for_bit(shape):
         a2 = ev.eval(planes[: n // 3 + 1])
         assert ev.stats()["saturated"] == 0
     assert (a2[0] == a[0][: n // 3 + 1]).all() and (a2[1] == a[1][: n // 3 + 1]).all()
-    with wino_eval(blob, max(n, 192), "k8") as ev:  # the eight-wave kernel (two waves per SIMD; built, measured, not the default)
-        assert ev.tower_kernel() == "conv3x3_wino8_kernel"
-        c8 = ev.eval(planes)
-        assert ev.stats()["saturated"] == 0
-    assert (a[0] == c8[0]).all() and (a[1] == c8[1]).all()
     if filters % 128 == 0:
         with wino_eval(blob, max(n, 192), "k16") as ev:
             assert ev.tower_kernel() == "conv3x3_wino_kernel"
