@@ -30,6 +30,7 @@
 #include "../../include/cattus_hip.h"
 #include "../../include/cattus_hip_diag.h"
 #include "kernels.h"
+#include "weight_layout.h"
 
 // Kernel arguments in device memory: by default the HIP runtime keeps the kernel-argument ring in host memory and the
 // command processor fetches every launch's arguments over the host link before the first wave starts (~1.6 us per
@@ -70,23 +71,10 @@ constexpr size_t HEADER_BYTES = 64;
 constexpr float BN_EPS = 1e-5f;
 constexpr uint32_t FC_HIDDEN = 128;
 
-inline uint16_t f32_to_bf16(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // keep NaN a NaN
-    u += 0x7fffu + ((u >> 16) & 1u);                                           // round to nearest even
-    return (uint16_t)(u >> 16);
-}
-
 // BatchNorm (eval) folded into the preceding bias-free conv:
 //   scale = gamma / sqrtf(var + eps);  w' = w * scale;  b' = beta - mean * scale
 // (gamma = 1, beta = 0 where the reference builds BatchNorm2d(affine=False): net_utils.py:14,30,68,78).
-// This file is compiled with -ffp-contract=off: the products and the subtraction round separately.
-struct Folded {
-    std::vector<float> w;  // [taps][cout][cin]
-    std::vector<float> b;  // [cout]
-};
-
+// This file is compiled with -ffp-contract=off: the products and the subtraction round separately.  (Folded: weight_layout.h)
 Folded fold_conv(const float* w, uint32_t cout, uint32_t cin, uint32_t taps, const float* gamma, const float* beta,
                  const float* mean, const float* var) {
     Folded f;
@@ -250,12 +238,7 @@ bool is_pinned(const void* p) {
     return (const char*)p < it->first + it->second;
 }
 
-struct ConvLayer {
-    DevBuf w, b;
-    DevBuf wf;  // f16x2: the same weights in MFMA fragment order (kernels.h, CONV_W_FRAG)
-    DevBuf wu, bw;  // f16x2, Winograd form: G g G^T as scaled (hi, lo) pairs in fragment order, and its [biases | inverse scales]
-    uint32_t cin = 0;  // as laid out on the device (padded for the MFMA path)
-};
+struct ConvLayer { DevBuf w, b; };  // in the one layout the tower's kernel reads this layer in (upload_conv)
 
 struct ServerBatch {
     uint64_t seq = 0;
@@ -282,12 +265,39 @@ struct Lane {
     // page-locked word the error word is copied to behind every such launch
     DevBuf tower_layers, tower_ready;  // tower_ready: [error word, pad to 64 B | a counter per (layer, board group)] -- one memset per batch
     PinnedBuf h_tower_err;
-    uint32_t tower_nlayers = 0;
     std::mutex mu;  // held while a batch uses the lane
     ~Lane() {
         if (done) (void)hipEventDestroy(done);
         if (stream) (void)hipStreamDestroy(stream);
     }
+};
+
+// Which tower an evaluator runs: resolved once, by resolve_plan() in cattus_hip_create, never per batch (a leaf's result must not depend
+// on the batch it came in).  Everything that differs between the paths -- what is uploaded, allocated, launched, reported -- reads this.
+enum class TowerKind {
+    // SimpleTwoHeadedModel (training/cattus_train/net_utils.py:92-121; blob with filters == 0): planes -> f32 tensor -> two dense layers
+    // + ReLU -> a dense tanh value head and a dense policy head, all in f32 whatever cfg.dtype says (the net is tiny)
+    Simple,
+    Generic,     // NCHW f32 SIMT tower: heads wider than one 32-row MFMA tile, or the checker (CATTUS_FORCE_GENERIC=1)
+    PerLayer,    // MFMA NHWC tower, one launch per conv layer (any dtype)
+    Resident64,  // bf16, <= 64 filters: the whole tower in one launch, activations resident in LDS (tower64_lds_kernel; CATTUS_TOWER64=0: PerLayer)
+    Resident64Split,  // f16x2, <= 64 filters: the same in split precision (tower64_split_kernel; weights from the register ring)
+    // f16x2, 8x8 boards: every layer behind the stem in Winograd F(2x2, 3x3) form, for max_batch > 128 (up to there the direct kernels'
+    // small tiles win or tie -- whole step of chess 20x256, direct | Winograd: 0.59 | 0.89 ms at 64 leaves, 0.87 | 0.89 at 96, 0.97 | 0.90 at
+    // 128 full and ~0.87 | 0.89 at the ~93 a 128-leaf self-play batch holds; from 129 on the direct form needs a second 128-row tile: 1.45 |
+    // 0.93 at 160, 1.53 | 1.01 at 192, 1.77 | 1.25 at 256, scripts/by_batch_forms.py); cattus_eval_config.tower_form forbids / forces it.
+    Wino16,  // the 16-frequencies kernel (kernels_wino.hip)
+    Wino4,   // the 4-frequencies x 2x2-blocks kernel (kernels_wino4.hip) wherever it covers the shape; same bits (CATTUS_WINO_KERNEL=k16|k4)
+};
+struct TowerPlan {
+    TowerKind kind = TowerKind::Generic;
+    bool w_frag = false;   // f16x2 weights in fragment order for the register-ring kernels (CATTUS_SPLIT_W=0: rows, through the LDS ring)
+    bool inplace = false;  // Winograd kinds: a block's output over its own skip rows (CATTUS_WINO_INPLACE=0: a third activation buffer)
+    // Wino4: every layer behind the stem as ONE launch (tower_wino4_kernel), one workgroup per CU, several tiles per workgroup and layer where
+    // a layer has more tiles than the device has CUs (CATTUS_WINO_PERSIST=0: per-layer launches) -- for the batches one_launch_now() admits
+    bool one_launch = false;
+    bool tuned() const { return kind != TowerKind::Simple && kind != TowerKind::Generic; }  // the MFMA NHWC towers
+    bool wino() const { return kind == TowerKind::Wino16 || kind == TowerKind::Wino4; }
 };
 
 }  // namespace
@@ -296,48 +306,22 @@ struct cattus_eval {
     DevArena arena;  // first member: destroyed last, behind every buffer carved from it
     cattus_net_desc d{};
     cattus_eval_config cfg{};
-    bool tuned = false;  // MFMA NHWC tower vs generic NCHW f32 tower
-    // SimpleTwoHeadedModel (training/cattus_train/net_utils.py:92-121; blob with filters == 0): planes -> f32 tensor -> two dense
-    // layers + ReLU -> a dense tanh value head and a dense policy head, all in f32 whatever cfg.dtype says (the net is tiny)
-    bool simple = false;
-    DevBuf d1w, d1b, d2w, d2b, svw, svb, spw, spb;
+    TowerPlan plan;
+    DevBuf d1w, d1b, d2w, d2b, svw, svb, spw, spb;  // TowerKind::Simple
     bool wait_spin = true;  // host wait for a batch: spinning hipStreamSynchronize, or a blocking event
     Act act = Act::F32;
     uint32_t hw = 0, bpad = 0, cpad0 = 0;
     uint32_t slots = 64;  // pixel slots per board of the tuned tower (kernels.h: tower_slots)
     uint32_t fpad = 0;    // filters as laid out on the device: rounded up to 64 on the tuned path (zero channels)
-    // bf16 networks with <= 64 filters: the whole tower in one launch, activations resident in LDS
-    // (tower64_lds_kernel; CATTUS_TOWER64=0 selects the per-layer launches, for A/B runs and the equality test)
-    bool tower64 = false;
-    bool resident_tower = true;  // diagnostic switch CATTUS_TOWER64=0: per-layer launches instead (A/B runs, the equality tests)
-    DevBuf t64_layers;
-    // f16x2 networks with <= 64 filters: the same, in split precision (tower64_split_kernel; weights from the register ring)
-    bool tower64s = false;
-    DevBuf t64s_bias;
+    DevBuf t64_layers, t64s_bias;  // the resident towers' layer table; Resident64Split: every layer's [biases | inverse scales]
     bool t64s_fuse_heads = true;  // CATTUS_T64S_HEADS=0: the head convs as their own launch on the tower's f32 rows (A/B, the equality test)
     int t64s_depth = 0;           // CATTUS_T64S_SHAPE=1|2: workgroup shape of the resident split tower (kernels.h; 0: by grid size)
     bool pack_separately = false;  // CATTUS_FUSED_STEM=0: plane pack as its own launch in front of the stem (A/B, tests)
     int t64_force_ch = 0;          // CATTUS_T64_CH=2|4: workgroup shape of the resident tower (A/B runs, the row-split test)
-    // f16x2, 8x8 boards, filters a multiple of 128: every layer behind the stem in Winograd F(2x2, 3x3) form (kernels_wino.hip).
-    // Chosen once, when the evaluator is created -- never per batch, so that a leaf's result does not depend on the batch it came
-    // in: for max_batch > 128 (up to there the direct kernels' small tiles win or tie -- whole step of chess 20x256, direct | Winograd: 0.59 |
-    // 0.89 ms at 64 leaves, 0.87 | 0.89 at 96, 0.97 | 0.90 at 128 full and ~0.87 | 0.89 at the ~93 a 128-leaf self-play batch holds; from 129 on
-    // the direct form needs a second 128-row tile: 1.45 | 0.93 at 160, 1.53 | 1.01 at 192, 1.77 | 1.25 at 256, scripts/by_batch_forms.py);
-    // cattus_eval_config.tower_form forbids / forces it.
-    bool winograd = false;
-    // which Winograd kernel: the 4-frequencies x 2x2-blocks one (kernels_wino4.hip) wherever it covers the shape, else the
-    // 16-frequencies one (kernels_wino.hip); same bits; diagnostic switch CATTUS_WINO_KERNEL=k16|k4
-    bool wino_k4 = true;
-    // The Winograd tower as ONE launch (tower_wino4_kernel), one workgroup per CU, several tiles per workgroup and layer where a layer has
-    // more tiles than the device has CUs (diagnostic switch
-    // CATTUS_WINO_PERSIST=0: per-layer launches; CATTUS_WINO_SPIN=<polls>: the budget of a hand-off wait).  persist_ok falls when
-    // a launch reported a wait that gave up: the batch is run again on the per-layer launches, and so is every later one.
-    bool wino_persist = true;
-    std::atomic<bool> persist_ok{true};
-    uint32_t persist_spin = 1u << 18;
-    uint32_t cus = 0;
-    bool wino_inplace = true;      // CATTUS_WINO_INPLACE=0: a third activation buffer for the blocks' outputs (A/B runs)
-    bool split_wfrag = true;       // CATTUS_SPLIT_W=0: f16x2 weights through the LDS ring (conv3x3_split_kernel) instead of the register ring
+    // the one-launch Winograd tower: set when a launch reported a hand-off wait that gave up (CATTUS_WINO_SPIN=<polls>: the budget of a
+    // wait) -- that batch is run again on the per-layer launches, and so is every later one
+    std::atomic<bool> tower_gave_up{false};
+    uint32_t persist_spin = 1u << 18, cus = 0;
     // the f16 towers carry the residual stream at 2^stream_shift times its size (choose_stream_shift); CATTUS_STREAM_SHIFT=0: never
     bool stream_shift_on = true;
     int stream_shift = 0;
@@ -400,11 +384,6 @@ size_t blob_floats(const cattus_net_desc& d) {
     return n;
 }
 
-// The Winograd kernel this evaluator would run a cin -> cout layer on covers that shape.
-bool wino_shape_ok(const cattus_eval* e, uint32_t cin, uint32_t cout) {
-    return e->wino_k4 ? wino4_supported(e->bpad, cin, cout, e->d.board) : wino_supported(e->bpad, cin, cout, e->d.board);
-}
-
 // Launches of the persistent tower never overlap on a device: each waits for the one before it (an event chain per device, process-wide:
 // two evaluators -- model1 and model2 of a self-play round -- or the two lanes of one would otherwise share the CUs, neither launch
 // would have all its workgroups resident, and each would wait for hand-offs from workgroups the other keeps out).  Other work of the
@@ -424,140 +403,41 @@ int chain_persistent_launch(int device, hipStream_t st, const std::function<void
     return CATTUS_OK;
 }
 
-// Upload one folded 3x3 layer in the layout of the selected tower.  On the tuned path output channels are
-// padded to `cout_pad` and input channels to the device layout of the producing layer (`cin_pad`, a multiple of
-// one 128-byte row) with zero weights and zero bias: a padded channel computes relu(0) = 0, and as an input it
-// adds fmaf(0, x, acc) = acc terms only, so the f32 chains of the real channels are bit for bit unchanged.
-int upload_conv(cattus_eval* e, ConvLayer& L, const Folded& f, uint32_t cout, uint32_t cin, uint32_t cout_pad, uint32_t cin_pad) {
+// Upload one folded 3x3 layer in the layout this evaluator's tower reads it in (weight_layout.h): L.w the weights, L.b the biases (f16 towers:
+// [biases | inverse scales] of that layout's scaling).  The Winograd kinds run every layer behind the stem on U = G g G^T, kept in the arena.
+int upload_conv(cattus_eval* e, ConvLayer& L, const Folded& f, uint32_t cout, uint32_t cin, bool stem = false) {
+    auto up = [](DevBuf& buf, const auto& v, DevArena* arena = nullptr) { return buf.upload(v.data(), v.size() * sizeof(v[0]), arena); };
     int rc;
-    if (!e->tuned) {
-        L.cin = cin;
-        if ((rc = L.b.upload(f.b.data(), cout * sizeof(float)))) return rc;
-        return L.w.upload(f.w.data(), f.w.size() * sizeof(float));
+    if (!e->plan.tuned()) return (rc = up(L.b, f.b)) ? rc : up(L.w, f.w);
+    const ConvShape s{cout, cin, e->fpad, stem ? e->cpad0 : e->fpad};
+    if (e->plan.wino() && !stem) {
+        std::vector<int> sh;
+        const std::vector<double> U = wino_transform(f, s, &sh);
+        if ((rc = up(L.b, bias_and_scales(f, s, &sh)))) return rc;
+        return up(L.w, wino_u(U, s, sh), &e->arena);
     }
-    L.cin = cin_pad;
-    if (e->act == Act::F16S) {
-        // Split precision (kernels.hip, K1s): a weight is the pair hi = f16(w'), lo = f16(w' - hi) of w' = w * 2^s, with
-        // s chosen per output channel so that the channel's largest |w'| lies in [2^10, 2^11): the lo halves of all but
-        // the channel's tiniest weights are then normal f16 numbers (22 significant bits per weight), nothing comes near
-        // the f16 range limit, and 2^-s -- applied to the f32 accumulator in the epilogue -- undoes the scale exactly.
-        // Rows are [hi of 32 input channels | lo of the same 32] per 128 bytes; the bias buffer is [cout_pad biases |
-        // cout_pad inverse scales].
-        std::vector<float> b((size_t)2 * cout_pad, 0.0f);
-        memcpy(b.data(), f.b.data(), cout * sizeof(float));
-        std::vector<_Float16> w((size_t)9 * cout_pad * 2 * cin_pad, (_Float16)0.0f);
-        for (uint32_t co = 0; co < cout_pad; co++) {
-            float m = 0.0f;
-            if (co < cout)
-                for (uint32_t t = 0; t < 9; t++)
-                    for (uint32_t ci = 0; ci < cin; ci++) m = std::max(m, fabsf(f.w[((size_t)t * cout + co) * cin + ci]));
-            int sh = 0;
-            if (m > 0.0f && std::isfinite(m)) sh = std::min(100, std::max(-100, 10 - ilogbf(m)));
-            b[cout_pad + co] = ldexpf(1.0f, -sh);
-            if (co >= cout) continue;
-            for (uint32_t t = 0; t < 9; t++)
-                for (uint32_t ci = 0; ci < cin; ci++) {
-                    const float ws = ldexpf(f.w[((size_t)t * cout + co) * cin + ci], sh);
-                    const _Float16 hi = (_Float16)ws;
-                    const _Float16 lo = (_Float16)(ws - (float)hi);
-                    _Float16* row = &w[((size_t)t * cout_pad + co) * 2 * cin_pad + (size_t)(ci >> 5) * 64 + (ci & 31)];
-                    row[0] = hi, row[32] = lo;
-                }
-        }
-        if ((rc = L.b.upload(b.data(), b.size() * sizeof(float)))) return rc;
-        if (e->winograd && &L != &e->stem && wino_shape_ok(e, cin_pad, cout_pad)) {
-            // Winograd F(2x2, 3x3) form: U = G g G^T per (cout, cin) in float64, one power-of-two scale per output channel over
-            // all 16 frequencies (largest |U 2^s| in [2^10, 2^11)), split into (hi, lo), in the kernel's fragment order
-            static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-            std::vector<double> U((size_t)cout * cin * 16);
-            std::vector<float> bwv((size_t)2 * cout_pad, 0.0f);
-            memcpy(bwv.data(), f.b.data(), cout * sizeof(float));
-            std::vector<_Float16> wu((size_t)16 * cout_pad * cin_pad * 2 + (size_t)WINO_RING_STAGES * 1024, (_Float16)0.0f);  // + the ring's overrun
-            for (uint32_t co = 0; co < cout_pad; co++) {
-                double m = 0.0;
-                if (co < cout)
-                    for (uint32_t ci = 0; ci < cin; ci++) {
-                        double g[3][3], t[4][3];
-                        for (int ky = 0; ky < 3; ky++)
-                            for (int kx = 0; kx < 3; kx++) g[ky][kx] = f.w[((size_t)(ky * 3 + kx) * cout + co) * cin + ci];
-                        for (int i = 0; i < 4; i++)
-                            for (int kx = 0; kx < 3; kx++) t[i][kx] = G[i][0] * g[0][kx] + G[i][1] * g[1][kx] + G[i][2] * g[2][kx];
-                        for (int i = 0; i < 4; i++)
-                            for (int l = 0; l < 4; l++) {
-                                const double u = t[i][0] * G[l][0] + t[i][1] * G[l][1] + t[i][2] * G[l][2];
-                                U[((size_t)co * cin + ci) * 16 + i * 4 + l] = u;
-                                m = std::max(m, fabs(u));
-                            }
-                    }
-                int sh = 0;
-                if (m > 0.0 && std::isfinite(m)) sh = std::min(100, std::max(-100, 10 - ilogb(m)));
-                bwv[cout_pad + co] = ldexpf(1.0f, -sh);
-                if (co >= cout) continue;
-                for (uint32_t ci = 0; ci < cin; ci++)
-                    for (uint32_t fq = 0; fq < 16; fq++) {
-                        const float us = (float)ldexp(U[((size_t)co * cin + ci) * 16 + fq], sh);
-                        const _Float16 hi = (_Float16)us;
-                        wu[wino_frag_index(fq, co, ci, 0, cin_pad)] = hi;
-                        wu[wino_frag_index(fq, co, ci, 1, cin_pad)] = (_Float16)(us - (float)hi);
-                    }
-            }
-            if ((rc = L.bw.upload(bwv.data(), bwv.size() * sizeof(float)))) return rc;
-            if ((rc = L.wu.upload(wu.data(), wu.size() * 2, &e->arena))) return rc;
-        }
-        if (e->split_wfrag) {  // the register-ring kernel's layout: a permutation of the rows above
-            std::vector<_Float16> wf(w.size());
-            for (uint32_t t = 0; t < 9; t++)
-                for (uint32_t co = 0; co < cout_pad; co++) {
-                    const _Float16* row = &w[((size_t)t * cout_pad + co) * 2 * cin_pad];
-                    for (uint32_t ci = 0; ci < cin_pad; ci++) {
-                        wf[split_frag_index(t, co, ci, 0, cin_pad)] = row[(size_t)(ci >> 5) * 64 + (ci & 31)];
-                        wf[split_frag_index(t, co, ci, 1, cin_pad)] = row[(size_t)(ci >> 5) * 64 + (ci & 31) + 32];
-                    }
-                }
-            return L.wf.upload(wf.data(), wf.size() * 2);
-        }
-        return L.w.upload(w.data(), w.size() * 2);
-    }
-    if (e->act == Act::F16) {
-        // Single-term f16: w' = f16(w * 2^s), s per output channel as for the split tower (largest |w'| in [2^10, 2^11): no
-        // weight of the channel becomes a subnormal unless it is 2^-24 of the largest), rows [9][cout_pad][cin_pad] as in the
-        // bf16 tower; the bias buffer is [cout_pad biases | cout_pad inverse scales].
-        std::vector<float> b((size_t)2 * cout_pad, 0.0f);
-        memcpy(b.data(), f.b.data(), cout * sizeof(float));
-        std::vector<_Float16> w((size_t)9 * cout_pad * cin_pad, (_Float16)0.0f);
-        for (uint32_t co = 0; co < cout_pad; co++) {
-            float m = 0.0f;
-            if (co < cout)
-                for (uint32_t t = 0; t < 9; t++)
-                    for (uint32_t ci = 0; ci < cin; ci++) m = std::max(m, fabsf(f.w[((size_t)t * cout + co) * cin + ci]));
-            int sh = 0;
-            if (m > 0.0f && std::isfinite(m)) sh = std::min(100, std::max(-100, 10 - ilogbf(m)));
-            b[cout_pad + co] = ldexpf(1.0f, -sh);
-            if (co >= cout) continue;
-            for (uint32_t t = 0; t < 9; t++)
-                for (uint32_t ci = 0; ci < cin; ci++)
-                    w[((size_t)t * cout_pad + co) * cin_pad + ci] = (_Float16)ldexpf(f.w[((size_t)t * cout + co) * cin + ci], sh);
-        }
-        if ((rc = L.b.upload(b.data(), b.size() * sizeof(float)))) return rc;
-        return L.w.upload(w.data(), w.size() * 2);
-    }
-    std::vector<float> b(cout_pad, 0.0f);
-    memcpy(b.data(), f.b.data(), cout * sizeof(float));
-    if ((rc = L.b.upload(b.data(), b.size() * sizeof(float)))) return rc;
-    if (e->act == Act::BF16) {
-        std::vector<uint16_t> w((size_t)9 * cout_pad * cin_pad, 0);
-        for (uint32_t t = 0; t < 9; t++)
-            for (uint32_t co = 0; co < cout; co++)
-                for (uint32_t ci = 0; ci < cin; ci++)
-                    w[((size_t)t * cout_pad + co) * cin_pad + ci] = f32_to_bf16(f.w[((size_t)t * cout + co) * cin + ci]);
-        return L.w.upload(w.data(), w.size() * 2);
-    }
-    std::vector<float> w((size_t)9 * cout_pad * cin_pad, 0.0f);
-    for (uint32_t t = 0; t < 9; t++)
-        for (uint32_t co = 0; co < cout; co++)
-            memcpy(&w[((size_t)t * cout_pad + co) * cin_pad], &f.w[((size_t)t * cout + co) * cin], cin * sizeof(float));
-    return L.w.upload(w.data(), w.size() * 4);
+    const bool scaled = act_f16_family(e->act);
+    const std::vector<int> sh = scaled ? channel_shifts(f, s) : std::vector<int>();
+    if ((rc = up(L.b, bias_and_scales(f, s, scaled ? &sh : nullptr)))) return rc;
+    if (e->act == Act::F32) return up(L.w, rows_f32(f, s));
+    if (e->act == Act::BF16) return up(L.w, rows_bf16(f, s));
+    if (e->act == Act::F16) return up(L.w, rows_f16(f, s, sh));
+    return e->plan.w_frag ? up(L.w, frag_f16x2(f, s, sh)) : up(L.w, rows_f16x2(f, s, sh));
 }
+
+// What a lane has whichever tower runs: its stream and event, a batch's planes, logits and values on the device and in page-locked memory.
+int lane_common(cattus_eval* e, Lane& L) {
+    const size_t B = e->cfg.max_batch, M = e->d.moves, plane_bytes = B * e->d.planes * e->cfg.plane_words * 8;
+    int rc;
+    HIP_TRY(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&L.done, hipEventBlockingSync | hipEventDisableTiming));
+    if ((rc = L.d_planes.alloc(plane_bytes)) || (rc = L.d_policy.alloc(B * M * 4)) || (rc = L.d_value.alloc(B * 4))) return rc;
+    if ((rc = L.h_planes.alloc(plane_bytes)) || (rc = L.h_policy.alloc(B * M * 4)) || (rc = L.h_value.alloc(B * 4))) return rc;
+    return CATTUS_OK;
+}
+
+// leaf capacity of the tuned heads' activation buffer (HeadsMfma::hv): whole 32-leaf tiles
+uint32_t hv_leaves(const cattus_eval* e) { return (e->bpad + 31) / 32 * 32; }
 
 // SimpleTwoHeadedModel: weights transposed to [k][n] (coalesced along n in the dense kernel), buffers for the planes tensor
 // and the two hidden layers.
@@ -571,56 +451,29 @@ int build_simple(cattus_eval* e, const float* p) {
         return buf.upload(t.data(), t.size() * 4);
     };
     int rc;
-    if ((rc = upload_t(e->d1w, p, K))) return rc;
-    p += K * K;
-    if ((rc = e->d1b.upload(p, K * 4))) return rc;
-    p += K;
-    if ((rc = upload_t(e->d2w, p, K))) return rc;
-    p += K * K;
-    if ((rc = e->d2b.upload(p, K * 4))) return rc;
-    p += K;
-    if ((rc = upload_t(e->svw, p, 1))) return rc;
-    p += K;
-    if ((rc = e->svb.upload(p, 4))) return rc;
-    p += 1;
-    if ((rc = upload_t(e->spw, p, M))) return rc;
-    p += M * K;
-    if ((rc = e->spb.upload(p, M * 4))) return rc;
-    for (Lane& L : e->lanes) {
-        HIP_TRY(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&L.done, hipEventBlockingSync | hipEventDisableTiming));
-        if ((rc = L.d_planes.alloc(B * d.planes * e->cfg.plane_words * 8))) return rc;
-        if ((rc = L.x0.alloc(B * K * 4))) return rc;
-        if ((rc = L.a.alloc(B * K * 4))) return rc;
-        if ((rc = L.t.alloc(B * K * 4))) return rc;
-        if ((rc = L.d_policy.alloc(B * M * 4))) return rc;
-        if ((rc = L.d_value.alloc(B * 4))) return rc;
-        if ((rc = L.h_planes.alloc(B * d.planes * e->cfg.plane_words * 8))) return rc;
-        if ((rc = L.h_policy.alloc(B * M * 4))) return rc;
-        if ((rc = L.h_value.alloc(B * 4))) return rc;
-    }
+    const float *w1 = p, *b1 = w1 + K * K, *w2 = b1 + K, *b2 = w2 + K * K, *vw = b2 + K, *vb = vw + K, *pw = vb + 1, *pb = pw + M * K;  // blob order
+    if ((rc = upload_t(e->d1w, w1, K)) || (rc = e->d1b.upload(b1, K * 4)) || (rc = upload_t(e->d2w, w2, K)) || (rc = e->d2b.upload(b2, K * 4)) ||
+        (rc = upload_t(e->svw, vw, 1)) || (rc = e->svb.upload(vb, 4)) || (rc = upload_t(e->spw, pw, M)) || (rc = e->spb.upload(pb, M * 4)))
+        return rc;
+    for (Lane& L : e->lanes)
+        if ((rc = lane_common(e, L)) || (rc = L.x0.alloc(B * K * 4)) || (rc = L.a.alloc(B * K * 4)) || (rc = L.t.alloc(B * K * 4))) return rc;
     return CATTUS_OK;
 }
 
 int build(cattus_eval* e, const float* p) {
     const cattus_net_desc& d = e->d;
-    if (e->simple) return build_simple(e, p);
+    const TowerPlan& plan = e->plan;
+    if (plan.kind == TowerKind::Simple) return build_simple(e, p);
     const uint32_t F = d.filters, hw = e->hw, FP = e->fpad;
-    auto take = [&](size_t n) {
-        const float* r = p;
-        p += n;
-        return r;
-    };
+    auto take = [&](size_t n) { return (p += n) - n; };  // the next n floats of the blob
     int rc;
     const int t = e->stream_shift = act_f16_family(e->act) && e->stream_shift_on ? choose_stream_shift(d, p) : 0;
     {
         const float* w = take((size_t)F * d.planes * 9);
         const float *g = take(F), *be = take(F), *mu = take(F), *var = take(F);
-        const uint32_t kc = e->tuned ? (uint32_t)act_kc(e->act) : 1;
         Folded f = fold_conv(w, F, d.planes, 9, g, be, mu, var);
         if (t) shift_folded(f, t, t);
-        if ((rc = upload_conv(e, e->stem, f, F, d.planes, FP, (d.planes + kc - 1) / kc * kc))) return rc;
-        e->cpad0 = e->stem.cin;
+        if ((rc = upload_conv(e, e->stem, f, F, d.planes, true))) return rc;
     }
     for (uint32_t i = 0; i < d.blocks; i++) {
         e->c1.emplace_back(new ConvLayer);
@@ -629,12 +482,12 @@ int build(cattus_eval* e, const float* p) {
         const float *mu1 = take(F), *var1 = take(F);
         Folded f1 = fold_conv(w1, F, F, 9, nullptr, nullptr, mu1, var1);
         if (t) shift_folded(f1, -t, 0);
-        if ((rc = upload_conv(e, *e->c1.back(), f1, F, F, FP, FP))) return rc;
+        if ((rc = upload_conv(e, *e->c1.back(), f1, F, F))) return rc;
         const float* w2 = take((size_t)F * F * 9);
         const float *g2 = take(F), *be2 = take(F), *mu2 = take(F), *var2 = take(F);
         Folded f2 = fold_conv(w2, F, F, 9, g2, be2, mu2, var2);
         if (t) shift_folded(f2, t, t);
-        if ((rc = upload_conv(e, *e->c2.back(), f2, F, F, FP, FP))) return rc;
+        if ((rc = upload_conv(e, *e->c2.back(), f2, F, F))) return rc;
     }
     // heads: value rows first, then policy rows, in one [vhc+phc][F] 1x1 conv
     std::vector<float> hw_w((size_t)(d.vhc + d.phc) * F), hw_b(std::max(32u, d.vhc + d.phc), 0.0f);  // bias padded to one 32-row tile
@@ -656,12 +509,10 @@ int build(cattus_eval* e, const float* p) {
     memcpy(hw_b.data(), fv.b.data(), fv.b.size() * 4);
     memcpy(hw_b.data() + fv.b.size(), fp.b.data(), fp.b.size() * 4);
     const uint32_t kv = d.vhc * hw, kp = d.phc * hw;
-    if ((rc = e->head_b.upload(hw_b.data(), hw_b.size() * 4))) return rc;
-    if ((rc = e->b1.upload(fc1_b, FC_HIDDEN * 4))) return rc;
-    if ((rc = e->w2.upload(fc2_w, FC_HIDDEN * 4))) return rc;
-    if ((rc = e->b2.upload(fc2_b, 4))) return rc;
-    if ((rc = e->bp.upload(pfc_b, d.moves * 4))) return rc;
-    if (e->tuned) {
+    if ((rc = e->head_b.upload(hw_b.data(), hw_b.size() * 4)) || (rc = e->b1.upload(fc1_b, FC_HIDDEN * 4)) || (rc = e->w2.upload(fc2_w, FC_HIDDEN * 4)) ||
+        (rc = e->b2.upload(fc2_b, 4)) || (rc = e->bp.upload(pfc_b, d.moves * 4)))
+        return rc;
+    if (plan.tuned()) {
         // K-contiguous matrices, K padded to 16 with zeros (zero terms do not change an fmaf chain)
         const uint32_t ocn = d.vhc + d.phc;
         e->kvp = (kv + 15) / 16 * 16;
@@ -688,40 +539,29 @@ int build(cattus_eval* e, const float* p) {
                         v[(size_t)row * K + k];
             return o;
         };
-        if ((rc = upload_t(e->head_w, cw))) return rc;
-        if ((rc = upload_t(e->w1t, frag_order(w1, FC_HIDDEN, e->kvp)))) return rc;
-        if ((rc = upload_t(e->wpt, frag_order(wp, m32, e->kpp)))) return rc;
+        if ((rc = upload_t(e->head_w, cw)) || (rc = upload_t(e->w1t, frag_order(w1, FC_HIDDEN, e->kvp))) || (rc = upload_t(e->wpt, frag_order(wp, m32, e->kpp)))) return rc;
     } else {
         std::vector<float> w1t((size_t)kv * FC_HIDDEN), wpt((size_t)kp * d.moves);
         for (uint32_t j = 0; j < FC_HIDDEN; j++)
             for (uint32_t k = 0; k < kv; k++) w1t[(size_t)k * FC_HIDDEN + j] = fc1_w[(size_t)j * kv + k];
         for (uint32_t m = 0; m < d.moves; m++)
             for (uint32_t k = 0; k < kp; k++) wpt[(size_t)k * d.moves + m] = pfc_w[(size_t)m * kp + k];
-        if ((rc = e->head_w.upload(hw_w.data(), hw_w.size() * 4))) return rc;
-        if ((rc = e->w1t.upload(w1t.data(), w1t.size() * 4))) return rc;
-        if ((rc = e->wpt.upload(wpt.data(), wpt.size() * 4))) return rc;
+        if ((rc = e->head_w.upload(hw_w.data(), hw_w.size() * 4)) || (rc = e->w1t.upload(w1t.data(), w1t.size() * 4)) || (rc = e->wpt.upload(wpt.data(), wpt.size() * 4))) return rc;
         e->kvp = kv, e->kpp = kp;
     }
 
-    if (e->tuned && e->act == Act::BF16 && FP == 64 && e->cpad0 == 64) {
-        e->tower64 = e->resident_tower;
-        std::vector<Tower64Layer> tl;
-        tl.push_back(Tower64Layer{e->stem.w.p, e->stem.b.as<float>(), 0, 0});
-        for (uint32_t i = 0; i < d.blocks; i++) {
-            tl.push_back(Tower64Layer{e->c1[i]->w.p, e->c1[i]->b.as<float>(), 0, 0});
-            tl.push_back(Tower64Layer{e->c2[i]->w.p, e->c2[i]->b.as<float>(), 1, 0});
-        }
+    // the resident towers' layer tables: stem, then (conv1, conv2 + skip) per block
+    auto layer_table = [&](auto row) {
+        std::vector<decltype(row(e->stem, 0, true))> tl{row(e->stem, 0, true)};
+        for (uint32_t i = 0; i < d.blocks; i++) tl.push_back(row(*e->c1[i], 0, false)), tl.push_back(row(*e->c2[i], 1, false));
+        return tl;
+    };
+    if (plan.kind == TowerKind::Resident64) {
+        const auto tl = layer_table([](const ConvLayer& c, int res, bool) { return Tower64Layer{c.w.p, c.b.as<float>(), res, 0}; });
         if ((rc = e->t64_layers.upload(tl.data(), tl.size() * sizeof(Tower64Layer)))) return rc;
     }
-
-    if (e->tuned && e->act == Act::F16S && FP == 64 && e->cpad0 == 32 && e->split_wfrag && 1 + 2 * d.blocks <= (uint32_t)T64S_MAX_LAYERS) {
-        e->tower64s = e->resident_tower;
-        std::vector<Tower64SplitLayer> tl;
-        tl.push_back(Tower64SplitLayer{e->stem.wf.p, e->stem.b.as<float>(), 0, 1});
-        for (uint32_t i = 0; i < d.blocks; i++) {
-            tl.push_back(Tower64SplitLayer{e->c1[i]->wf.p, e->c1[i]->b.as<float>(), 0, 2});
-            tl.push_back(Tower64SplitLayer{e->c2[i]->wf.p, e->c2[i]->b.as<float>(), 1, 2});
-        }
+    if (plan.kind == TowerKind::Resident64Split) {
+        const auto tl = layer_table([](const ConvLayer& c, int res, bool stem) { return Tower64SplitLayer{c.w.p, c.b.as<float>(), res, stem ? 1 : 2}; });
         if ((rc = e->t64_layers.upload(tl.data(), tl.size() * sizeof(Tower64SplitLayer)))) return rc;
         // every layer's [64 biases | 64 inverse scales] in one table (the kernel copies it to LDS with independent loads)
         if ((rc = e->t64s_bias.alloc(tl.size() * 512))) return rc;
@@ -730,205 +570,238 @@ int build(cattus_eval* e, const float* p) {
     }
 
     // activations
-    const size_t bp_ = e->bpad, B = e->cfg.max_batch;
+    const bool tuned = plan.tuned();
     // bytes per channel of the tower buffers; the f16 towers' last layer writes f32 rows into one of them
-    const size_t esz = e->tuned ? (act_f16_family(e->act) ? 4 : (size_t)act_bytes(e->act)) : 4;
-    const size_t hesz = e->tuned ? (size_t)act_bytes(head_act(e->act)) : 4;  // element of the head activations
-    const size_t slots = e->tuned ? e->slots : hw;
-    const size_t FA = e->tuned ? FP : F;  // channels of the tower buffers
+    const size_t bpad = e->bpad, esz = tuned ? (act_f16_family(e->act) ? 4 : (size_t)act_bytes(e->act)) : 4;
+    const size_t hesz = tuned ? (size_t)act_bytes(head_act(e->act)) : 4;  // element of the head activations
+    const size_t slots = tuned ? e->slots : hw;
     for (Lane& L : e->lanes) {
-        HIP_TRY(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&L.done, hipEventBlockingSync | hipEventDisableTiming));
-        if ((rc = L.d_planes.alloc(B * d.planes * e->cfg.plane_words * 8))) return rc;
-        if ((rc = L.x0.alloc(bp_ * slots * e->cpad0 * esz))) return rc;
-        if ((rc = L.a.alloc(bp_ * slots * FA * esz, &e->arena))) return rc;
-        if ((rc = L.t.alloc(bp_ * slots * FA * esz, &e->arena))) return rc;
-        if ((rc = L.y.alloc(bp_ * slots * FA * esz, e->wino_inplace ? nullptr : &e->arena))) return rc;  // in place: the Winograd tower does not touch it
-        const size_t hv_bytes = (size_t)(e->tuned ? (bp_ + 31) / 32 * 32 : bp_) * (e->kvp + e->kpp) * hesz;  // tuned: whole 32-leaf tiles
-        if ((rc = L.hv.alloc(hv_bytes))) return rc;
+        const size_t act_bytes_ = bpad * slots * FP * esz, hv_bytes = (size_t)(tuned ? hv_leaves(e) : bpad) * (e->kvp + e->kpp) * hesz;
+        if ((rc = lane_common(e, L)) || (rc = L.x0.alloc(bpad * slots * e->cpad0 * esz)) || (rc = L.a.alloc(act_bytes_, &e->arena)) ||
+            (rc = L.t.alloc(act_bytes_, &e->arena)) || (rc = L.y.alloc(act_bytes_, plan.inplace ? nullptr : &e->arena)) ||  // in place: the Winograd tower does not touch y
+            (rc = L.hv.alloc(hv_bytes)) || (rc = L.h1.alloc(bpad * FC_HIDDEN * 4)))
+            return rc;
         HIP_TRY(hipMemset(L.hv.p, 0, hv_bytes));  // pad columns (and leaves never written) must read as zero
-        if ((rc = L.h1.alloc(bp_ * FC_HIDDEN * 4))) return rc;
-        if ((rc = L.d_policy.alloc(B * d.moves * 4))) return rc;
-        if ((rc = L.d_value.alloc(B * 4))) return rc;
-        if ((rc = L.h_planes.alloc(B * d.planes * e->cfg.plane_words * 8))) return rc;
-        if ((rc = L.h_policy.alloc(B * d.moves * 4))) return rc;
-        if ((rc = L.h_value.alloc(B * 4))) return rc;
-        if (e->tuned && e->act == Act::F16S && e->wino_k4 && e->wino_persist && e->wino_inplace && d.blocks > 0 && e->c1[0]->wu.p) {
+        if (plan.one_launch) {
             // the lane's layer table: conv1 of a block a -> t, conv2 t -> a over its own skip rows (the per-layer launches' in-place plan)
             std::vector<Wino4TowerLayer> tl;
+            float *la = L.a.as<float>(), *lt = L.t.as<float>();
             for (uint32_t i = 0; i < d.blocks; i++) {
-                tl.push_back(Wino4TowerLayer{L.a.as<float>(), e->c1[i]->wu.p, e->c1[i]->bw.as<float>(), nullptr, L.t.as<float>()});
-                tl.push_back(Wino4TowerLayer{L.t.as<float>(), e->c2[i]->wu.p, e->c2[i]->bw.as<float>(), L.a.as<float>(), L.a.as<float>()});
+                tl.push_back(Wino4TowerLayer{la, e->c1[i]->w.p, e->c1[i]->b.as<float>(), nullptr, lt});
+                tl.push_back(Wino4TowerLayer{lt, e->c2[i]->w.p, e->c2[i]->b.as<float>(), la, la});
             }
-            L.tower_nlayers = (uint32_t)tl.size();
-            if ((rc = L.tower_layers.upload(tl.data(), tl.size() * sizeof(Wino4TowerLayer)))) return rc;
-            if ((rc = L.tower_ready.alloc(64 + (size_t)tl.size() * (bp_ / 4) * 4))) return rc;
-            if ((rc = L.h_tower_err.alloc(4))) return rc;
+            if ((rc = L.tower_layers.upload(tl.data(), tl.size() * sizeof(Wino4TowerLayer))) || (rc = L.tower_ready.alloc(64 + (size_t)tl.size() * (bpad / 4) * 4)) ||
+                (rc = L.h_tower_err.alloc(4)))
+                return rc;
             *L.h_tower_err.as<unsigned>() = 0;
         }
     }
     return CATTUS_OK;
 }
 
-struct TowerTimer {
-    std::vector<hipEvent_t> ev;  // pairs
-    size_t used = 0;
-};
+struct TowerTimer { std::vector<hipEvent_t> ev; size_t used = 0; };  // event pairs (start, stop) and how many events a pass has taken
 
-// Enqueue the whole forward for n leaves whose planes are at d_planes; logits/values go to
-// d_policy/d_value.  With `tt`, a HIP event pair brackets every tower conv launch.
-int enqueue_forward(cattus_eval* e, Lane& L, const uint64_t* d_planes, uint32_t n, float* d_policy, float* d_value,
-                    hipStream_t st, TowerTimer* tt = nullptr) {
+// The two decisions about the one-launch Winograd tower that are taken per batch: the sticky demotion after a hand-off wait gave up, and whether
+// the grid of a batch of nb boards fits the device.  Both ways of launching give the same bits: a leaf's result still does not depend on its batch.
+bool one_launch_now(const cattus_eval* e, uint32_t nb) {
+    return e->plan.one_launch && !e->tower_gave_up.load(std::memory_order_relaxed) && wino4_tower_fits(nb, e->fpad, e->cus);
+}
+
+// One forward pass being enqueued on `st`: n leaves whose planes are at d_planes (nb boards with the tower's padding), logits and values to
+// d_policy / d_value.  One function per TowerKind; a tower returns its output rows, or nullptr where it has run the head convs itself.
+struct Forward {
+    cattus_eval* e;
+    Lane& L;
+    const uint64_t* d_planes;
+    uint32_t n, nb;
+    float *d_policy, *d_value;
+    hipStream_t st;
+    TowerTimer* tt;
     const cattus_net_desc& d = e->d;
-    const uint32_t F = d.filters, hw = e->hw, S = d.board, w64 = e->cfg.plane_words;
-    // timing pass: each tower launch gets its own (start, stop) event pair stamped by the kernel itself
-    auto ev = [&](bool stop) -> hipEvent_t {
-        if (!tt || tt->used >= tt->ev.size()) return nullptr;
-        (void)stop;
-        return tt->ev[tt->used++];
-    };
-    void *a = L.a.p, *t = L.t.p, *y = L.y.p;
-    uint32_t nb = n;
-    if (e->simple) {
-        // SimpleTwoHeadedModel.forward (net_utils.py:112-121): flatten -> dense + ReLU -> dense + ReLU -> value: dense + tanh,
-        // policy: dense + the non-finite scrub of net/mod.rs:56-61
-        const uint32_t K = d.planes * hw;
+    const uint32_t w64 = e->cfg.plane_words, S = d.board, F = d.filters, FP = e->fpad;
+    float *a = L.a.as<float>(), *t = L.t.as<float>(), *y = L.y.as<float>();
+
+    // with `tt` (a timing pass) each tower launch gets its own (start, stop) event pair stamped by the kernel itself
+    hipEvent_t ev() { return tt && tt->used < tt->ev.size() ? tt->ev[tt->used++] : nullptr; }
+
+    // SimpleTwoHeadedModel.forward (net_utils.py:112-121): flatten -> dense + ReLU -> dense + ReLU -> value: dense + tanh,
+    // policy: dense + the non-finite scrub of net/mod.rs:56-61
+    void simple() {
+        const uint32_t K = d.planes * e->hw;
         launch_planes_to_tensor_nchw(d_planes, n, d.planes, w64, S, n, L.x0.as<float>(), st);
-        launch_dense(L.x0.as<float>(), K, e->d1w.as<float>(), e->d1b.as<float>(), n, K, K, (float*)a, 1, st);
-        launch_dense((float*)a, K, e->d2w.as<float>(), e->d2b.as<float>(), n, K, K, (float*)t, 1, st);
-        launch_dense((float*)t, K, e->svw.as<float>(), e->svb.as<float>(), n, K, 1, d_value, 2, st);
-        launch_dense((float*)t, K, e->spw.as<float>(), e->spb.as<float>(), n, K, d.moves, d_policy, 0, st);
-        hipError_t serr = hipGetLastError();
-        if (serr != hipSuccess) return fail(CATTUS_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(serr));
-        return CATTUS_OK;
+        launch_dense(L.x0.as<float>(), K, e->d1w.as<float>(), e->d1b.as<float>(), n, K, K, a, 1, st);
+        launch_dense(a, K, e->d2w.as<float>(), e->d2b.as<float>(), n, K, K, t, 1, st);
+        launch_dense(t, K, e->svw.as<float>(), e->svb.as<float>(), n, K, 1, d_value, 2, st);
+        launch_dense(t, K, e->spw.as<float>(), e->spb.as<float>(), n, K, d.moves, d_policy, 0, st);
     }
-    if (e->tuned) {
-        const uint32_t bpw = ROWS_PER_WG / e->slots;  // boards per workgroup of the conv kernel
-        const uint32_t FP = e->fpad;
-        nb = (n + bpw - 1) / bpw * bpw;
-        if (e->tower64) {
-            Tower64Args ta{};
-            ta.planes = d_planes, ta.layers = e->t64_layers.as<Tower64Layer>(), ta.out = nullptr;
-            ta.n = n, ta.C = d.planes, ta.w64 = w64, ta.S = S, ta.nlayers = 1 + 2 * d.blocks;
-            ta.head_w = e->head_w.p, ta.head_b = e->head_b.as<float>(), ta.hv = L.hv.p;
-            ta.hv_pol = (uint32_t)((e->bpad + 31) / 32 * 32) * e->kvp, ta.kvp = e->kvp, ta.kpp = e->kpp, ta.vhc = d.vhc, ta.ocn = d.vhc + d.phc;
-            const uint32_t rows = nb * e->slots;
-            // 128-row workgroups; for 64-slot boards one board per workgroup while that leaves no CU with two of them
-            hipEvent_t s0 = ev(false), s1 = ev(true);
-            int ch = e->slots == 64 && rows / 64 <= 256 ? 4 : 2;
-            if (e->t64_force_ch) ch = e->t64_force_ch == 4 && e->slots == 64 ? 4 : 2;  // A/B runs, the row-split test
-            launch_tower64(ta, rows, ch, e->t64_layer_steps, st, s0, s1);
-        } else if (e->tower64s) {
-            // the whole split-precision tower in one launch; its output: plain f32 rows in `a` for the f32 head kernels
-            Tower64SplitArgs ta{};
-            ta.planes = d_planes, ta.layers = e->t64_layers.as<Tower64SplitLayer>(), ta.sat = e->conv_opts.saturated;
-            ta.bias_all = e->t64s_bias.as<float>();
-            ta.n = n, ta.C = d.planes, ta.w64 = w64, ta.S = S, ta.nlayers = 1 + 2 * d.blocks;
-            if (e->t64s_fuse_heads) {
-                ta.head_w = e->head_w.as<float>(), ta.head_b = e->head_b.as<float>(), ta.hv = L.hv.as<float>();
-                ta.hv_pol = (uint32_t)((e->bpad + 31) / 32 * 32) * e->kvp, ta.kvp = e->kvp, ta.kpp = e->kpp, ta.vhc = d.vhc, ta.ocn = d.vhc + d.phc;
-            } else {
-                ta.out = (float*)a;
-            }
-            hipEvent_t s0 = ev(false), s1 = ev(true);
-            launch_tower64_split(ta, nb * e->slots, e->t64s_depth, st, s0, s1);
-        } else {
-            // the stem conv expands the planes itself when they fit one 128-byte chunk (every game here); else K0 first
-            const bool fused_stem = d.planes <= 32 && e->cpad0 == (uint32_t)act_kc(e->act) && !e->pack_separately;
-            const StemInput stem_in{d_planes, n, d.planes, w64};
-            if (!fused_stem) launch_pack_planes_nhwc(e->act, d_planes, n, nb, d.planes, w64, S, e->cpad0, L.x0.p, st);
-            hipEvent_t s0 = ev(false), s1 = ev(true);
-            // the split tower hands its last layer to the f32 head kernels as plain f32 rows
-            const int last_flags = act_f16_family(e->act) ? CONV_OUT_F32 : 0;
-            const bool wfrag = e->act == Act::F16S && e->split_wfrag;
-            const int wflag = wfrag ? CONV_W_FRAG : 0;
-            auto wptr = [&](const ConvLayer& c) { return wfrag ? c.wf.p : c.w.p; };
-            launch_conv3x3_mfma(e->act, L.x0.p, wptr(e->stem), e->stem.b.as<float>(), nullptr, a, nb, e->cpad0, FP, S, st, s0, s1,
-                                fused_stem ? &stem_in : nullptr,
-                                wflag | (d.blocks == 0 ? last_flags : e->act == Act::F16S && e->c1[0]->wu.p ? CONV_OUT_F32 | CONV_WINO_IN : 0), e->conv_opts);
-            // f16x2 with CATTUS_WINOGRAD=1 on 8x8 boards: every layer behind the stem in Winograd form, f32 rows between the layers
-            const bool wino = d.blocks > 0 && e->c1[0]->wu.p != nullptr;
-            auto conv = [&](const ConvLayer& c, const void* in, const void* res, void* out, int lflags) {
-                hipEvent_t s0 = ev(false), s1 = ev(true);
-                if (wino && e->wino_k4) launch_conv3x3_wino4((const float*)in, c.wu.p, c.bw.as<float>(), (const float*)res, (float*)out, nb, FP, FP, st, s0, s1, e->conv_opts.saturated);
-                else if (wino) launch_conv3x3_wino((const float*)in, c.wu.p, c.bw.as<float>(), (const float*)res, (float*)out, nb, FP, FP, st, s0, s1, e->conv_opts.saturated);
-                else launch_conv3x3_mfma(e->act, in, wptr(c), c.b.as<float>(), res, out, nb, FP, FP, S, st, s0, s1, nullptr, wflag | lflags, e->conv_opts);
-            };
-            if (wino && L.tower_nlayers && e->persist_ok.load(std::memory_order_relaxed) && wino4_tower_fits(nb, FP, e->cus)) {
-                // every layer behind the stem in ONE launch: counters and error word zeroed ahead of it on the same stream, the error word
-                // copied to page-locked memory behind it (eval_host reads it when the batch is back; the device entry points at their next call)
-                hipEvent_t s0 = ev(false), s1 = ev(true);
-                unsigned* const tower_err = L.tower_ready.as<unsigned>();
-                HIP_TRY(hipMemsetAsync(L.tower_ready.p, 0, 64 + (size_t)L.tower_nlayers * (nb / 4) * 4, st));
-                int crc = chain_persistent_launch(e->device, st, [&] {
-                    launch_tower_wino4(L.tower_layers.as<Wino4TowerLayer>(), L.tower_nlayers, tower_err + 16, tower_err,
-                                       e->conv_opts.saturated, nb, FP, e->persist_spin, e->cus, st, s0, s1);
-                });
-                if (crc) return crc;
-                HIP_TRY(hipMemcpyAsync(L.h_tower_err.p, tower_err, 4, hipMemcpyDeviceToHost, st));
-            } else
-            for (uint32_t i = 0; i < d.blocks; i++) {
-                conv(*e->c1[i], a, nullptr, t, 0);
-                if (wino && e->wino_inplace) {
-                    // the block's output over its own skip rows, in place: the lane that adds a skip element is the lane that writes
-                    // that element, behind all its reads -- two activation buffers instead of three (33.6 instead of 50 MB per lane
-                    // of what a pass drags through the Infinity Cache beside the 168 MB of U)
-                    conv(*e->c2[i], t, a, a, 0);
-                    continue;
-                }
-                conv(*e->c2[i], t, a, y, i + 1 == d.blocks ? last_flags : 0);
-                std::swap(a, y);
-            }
-        }
-    } else {
+
+    const void* generic() {
         launch_planes_to_tensor_nchw(d_planes, n, d.planes, w64, S, n, L.x0.as<float>(), st);
-        hipEvent_t s0 = ev(false), s1 = ev(true);
-        launch_conv3x3_generic(L.x0.as<float>(), e->stem.w.as<float>(), e->stem.b.as<float>(), nullptr, (float*)a, n,
-                               d.planes, F, S, st, s0, s1);
+        auto conv = [&](const ConvLayer& c, const float* in, uint32_t cin, const float* res, float* out) {
+            hipEvent_t s0 = ev(), s1 = ev();
+            launch_conv3x3_generic(in, c.w.as<float>(), c.b.as<float>(), res, out, n, cin, F, S, st, s0, s1);
+        };
+        conv(e->stem, L.x0.as<float>(), d.planes, nullptr, a);
         for (uint32_t i = 0; i < d.blocks; i++) {
-            s0 = ev(false), s1 = ev(true);
-            launch_conv3x3_generic((float*)a, e->c1[i]->w.as<float>(), e->c1[i]->b.as<float>(), nullptr, (float*)t, n, F,
-                                   F, S, st, s0, s1);
-            s0 = ev(false), s1 = ev(true);
-            launch_conv3x3_generic((float*)t, e->c2[i]->w.as<float>(), e->c2[i]->b.as<float>(), (float*)a, (float*)y, n,
-                                   F, F, S, st, s0, s1);
+            conv(*e->c1[i], a, F, nullptr, t);
+            conv(*e->c2[i], t, F, a, y);
             std::swap(a, y);
         }
+        return a;
     }
-    const uint32_t kv = d.vhc * hw, kp = d.phc * hw;
-    if (e->tuned) {
+
+    // the arguments the two resident towers share: the network, and the head convs fused on the resident output
+    template <class Args>
+    void resident_args(Args& ta, bool fuse_heads) {
+        ta.planes = d_planes, ta.layers = (decltype(ta.layers))e->t64_layers.p;
+        ta.n = n, ta.C = d.planes, ta.w64 = w64, ta.S = S, ta.nlayers = 1 + 2 * d.blocks;
+        if (!fuse_heads) return;
+        ta.head_w = (decltype(ta.head_w))e->head_w.p, ta.hv = (decltype(ta.hv))L.hv.p;  // bf16 tower: bf16 behind void*; split tower: float*
+        ta.head_b = e->head_b.as<float>();
+        ta.hv_pol = hv_leaves(e) * e->kvp, ta.kvp = e->kvp, ta.kpp = e->kpp, ta.vhc = d.vhc, ta.ocn = d.vhc + d.phc;
+    }
+
+    void resident64() {
+        Tower64Args ta{};
+        resident_args(ta, true);
+        const uint32_t rows = nb * e->slots;
+        // 128-row workgroups; for 64-slot boards one board per workgroup while that leaves no CU with two of them
+        hipEvent_t s0 = ev(), s1 = ev();
+        int ch = e->slots == 64 && rows / 64 <= 256 ? 4 : 2;
+        if (e->t64_force_ch) ch = e->t64_force_ch == 4 && e->slots == 64 ? 4 : 2;  // A/B runs, the row-split test
+        launch_tower64(ta, rows, ch, e->t64_layer_steps, st, s0, s1);
+    }
+
+    // CATTUS_T64S_HEADS=0: the tower's output as plain f32 rows in `a` for the f32 head kernels
+    const void* resident64_split() {
+        Tower64SplitArgs ta{};
+        resident_args(ta, e->t64s_fuse_heads);
+        ta.sat = e->conv_opts.saturated, ta.bias_all = e->t64s_bias.as<float>();
+        if (!e->t64s_fuse_heads) ta.out = a;
+        hipEvent_t s0 = ev(), s1 = ev();
+        launch_tower64_split(ta, nb * e->slots, e->t64s_depth, st, s0, s1);
+        return ta.out;
+    }
+
+    // One direct conv layer of the MFMA tower; `stem`: from the planes (the stem conv expands them itself when they fit one 128-byte
+    // chunk -- every game here -- else K0 packs them first)
+    void conv_mfma(const ConvLayer& c, const void* in, const void* res, void* out, int flags, bool stem = false) {
+        const bool fused_stem = stem && d.planes <= 32 && e->cpad0 == (uint32_t)act_kc(e->act) && !e->pack_separately;
+        const StemInput stem_in{d_planes, n, d.planes, w64};
+        if (stem && !fused_stem) launch_pack_planes_nhwc(e->act, d_planes, n, nb, d.planes, w64, S, e->cpad0, L.x0.p, st);
+        hipEvent_t s0 = ev(), s1 = ev();
+        launch_conv3x3_mfma(e->act, in, c.w.p, c.b.as<float>(), res, out, nb, stem ? e->cpad0 : FP, FP, S, st, s0, s1, fused_stem ? &stem_in : nullptr,
+                            (e->plan.w_frag ? CONV_W_FRAG : 0) | flags, e->conv_opts);
+    }
+
+    const void* per_layer() {
+        const int last_flags = act_f16_family(e->act) ? CONV_OUT_F32 : 0;  // the f16 towers hand the f32 head kernels plain f32 rows
+        conv_mfma(e->stem, L.x0.p, nullptr, a, d.blocks == 0 ? last_flags : 0, true);
+        for (uint32_t i = 0; i < d.blocks; i++) {
+            conv_mfma(*e->c1[i], a, nullptr, t, 0);
+            conv_mfma(*e->c2[i], t, a, y, i + 1 == d.blocks ? last_flags : 0);
+            std::swap(a, y);
+        }
+        return a;
+    }
+
+    // Wino16 / Wino4: the stem on the direct kernel, every layer behind it in Winograd form, f32 rows between the layers
+    int wino() {
+        conv_mfma(e->stem, L.x0.p, nullptr, a, CONV_OUT_F32 | CONV_WINO_IN, true);
+        if (one_launch_now(e, nb)) {
+            // every layer behind the stem in ONE launch: counters and error word zeroed ahead of it on the same stream, the error word
+            // copied to page-locked memory behind it (eval_host reads it when the batch is back; the device entry points at their next call)
+            hipEvent_t s0 = ev(), s1 = ev();
+            unsigned* const tower_err = L.tower_ready.as<unsigned>();
+            HIP_TRY(hipMemsetAsync(L.tower_ready.p, 0, 64 + (size_t)2 * d.blocks * (nb / 4) * 4, st));
+            if (int crc = chain_persistent_launch(e->device, st, [&] {
+                    launch_tower_wino4(L.tower_layers.as<Wino4TowerLayer>(), 2 * d.blocks, tower_err + 16, tower_err, e->conv_opts.saturated, nb, FP,
+                                       e->persist_spin, e->cus, st, s0, s1);
+                }))
+                return crc;
+            HIP_TRY(hipMemcpyAsync(L.h_tower_err.p, tower_err, 4, hipMemcpyDeviceToHost, st));
+            return CATTUS_OK;
+        }
+        const auto launch = e->plan.kind == TowerKind::Wino4 ? launch_conv3x3_wino4 : launch_conv3x3_wino;
+        auto conv = [&](const ConvLayer& c, const float* in, const float* res, float* out) {
+            hipEvent_t s0 = ev(), s1 = ev();
+            launch(in, c.w.p, c.b.as<float>(), res, out, nb, FP, FP, st, s0, s1, e->conv_opts.saturated);
+        };
+        for (uint32_t i = 0; i < d.blocks; i++) {
+            conv(*e->c1[i], a, nullptr, t);
+            // in place: the block's output over its own skip rows -- the lane that adds a skip element writes that element, behind all its reads:
+            // two activation buffers instead of three (33.6 instead of 50 MB per lane of what a pass drags through the Infinity Cache beside 168 MB of U)
+            conv(*e->c2[i], t, a, e->plan.inplace ? a : y);
+            if (!e->plan.inplace) std::swap(a, y);
+        }
+        return CATTUS_OK;
+    }
+
+    void heads_mfma(const void* tower) {
         HeadsMfma hd{};
         hd.conv_w = e->head_w.p, hd.conv_b = e->head_b.as<float>(), hd.hv = L.hv.p;
         hd.w1 = e->w1t.p, hd.b1 = e->b1.as<float>(), hd.h1 = L.h1.as<float>();
         hd.wp = e->wpt.p, hd.bp = e->bp.as<float>(), hd.policy = d_policy;
-        hd.hw = hw, hd.vhc = d.vhc, hd.phc = d.phc, hd.kvp = e->kvp, hd.kpp = e->kpp, hd.M = d.moves;
+        hd.hw = e->hw, hd.vhc = d.vhc, hd.phc = d.phc, hd.kvp = e->kvp, hd.kpp = e->kpp, hd.M = d.moves;
         hd.w2 = e->w2.as<float>(), hd.b2 = e->b2.as<float>(), hd.value = d_value;
-        hd.slots = e->slots;
-        hd.hv_leaves = (e->bpad + 31) / 32 * 32;
-        launch_heads_mfma(head_act(e->act), e->tower64 || (e->tower64s && e->t64s_fuse_heads) ? nullptr : a, n, e->fpad, hd, st);
-    } else {
+        hd.slots = e->slots, hd.hv_leaves = hv_leaves(e);
+        launch_heads_mfma(head_act(e->act), tower, n, FP, hd, st);
+    }
+
+    void heads_generic(const void* tower) {
+        const uint32_t hw = e->hw, kv = d.vhc * hw, kp = d.phc * hw;
         TowerView tv;
-        tv.x = a, tv.act = Act::F32, tv.sb = F * hw, tv.sk = hw, tv.sp = 1;
+        tv.x = tower, tv.act = Act::F32, tv.sb = F * hw, tv.sk = hw, tv.sp = 1;
         launch_head_conv1x1(tv, e->head_w.as<float>(), e->head_b.as<float>(), n, F, d.vhc + d.phc, hw, L.hv.as<float>(), st);
         launch_value_fc1(L.hv.as<float>(), kv + kp, e->w1t.as<float>(), e->b1.as<float>(), n, kv, L.h1.as<float>(), st);
         launch_value_fc2_tanh(L.h1.as<float>(), e->w2.as<float>(), e->b2.as<float>(), n, d_value, st);
         launch_policy_fc(L.hv.as<float>(), kv + kp, kv, e->wpt.as<float>(), e->bp.as<float>(), n, kp, d.moves, d_policy, st);
     }
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(CATTUS_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(err));
+};
+
+int enqueue_forward(cattus_eval* e, Lane& L, const uint64_t* d_planes, uint32_t n, float* d_policy, float* d_value, hipStream_t st, TowerTimer* tt = nullptr) {
+    const uint32_t bpw = e->plan.tuned() ? ROWS_PER_WG / e->slots : 1;  // boards per workgroup of the conv kernel
+    Forward f{e, L, d_planes, n, (n + bpw - 1) / bpw * bpw, d_policy, d_value, st, tt};
+    switch (e->plan.kind) {
+        case TowerKind::Simple: f.simple(); break;
+        case TowerKind::Generic: f.heads_generic(f.generic()); break;
+        case TowerKind::PerLayer: f.heads_mfma(f.per_layer()); break;
+        case TowerKind::Resident64: f.resident64(), f.heads_mfma(nullptr); break;
+        case TowerKind::Resident64Split: f.heads_mfma(f.resident64_split()); break;
+        case TowerKind::Wino16:
+        case TowerKind::Wino4:
+            if (int rc = f.wino()) return rc;
+            f.heads_mfma(f.a);
+            break;
+    }
+    if (hipError_t err = hipGetLastError()) return fail(CATTUS_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(err));
     return CATTUS_OK;
 }
 
-void account(cattus_eval* e, uint32_t n, double seconds) {
+// seconds: of a batch whose wait was measured; nullptr: the counters alone (an asynchronous entry point measures no time)
+void account(cattus_eval* e, uint32_t n, const double* seconds) {
     std::lock_guard<std::mutex> lk(e->stat_mu);
     cattus_stats& s = e->stats;
-    // RunningAverage::set with epsilon 0.99, starting from 0 (reference: engine/src/util/metric.rs:1-20,
-    // engine/src/net/mod.rs:36): value = (1 - eps) * value + eps * new
-    s.run_seconds_ema = 0.01 * s.run_seconds_ema + 0.99 * seconds;
-    s.run_seconds_total += seconds;
+    if (seconds) {
+        // RunningAverage::set with epsilon 0.99, starting from 0 (reference: engine/src/util/metric.rs:1-20,
+        // engine/src/net/mod.rs:36): value = (1 - eps) * value + eps * new
+        s.run_seconds_ema = 0.01 * s.run_seconds_ema + 0.99 * *seconds;
+        s.run_seconds_total += *seconds;
+    }
     s.batches += 1;
     s.positions += n;
     if (n == e->cfg.max_batch) s.full_batches += 1;
+}
+
+// True: a one-launch tower on this lane reported that a hand-off wait ran out of its budget (its workgroups were not all resident: somebody else's
+// kernels on this device) and finished on rows that were not ready.  Nothing of it is kept; every later batch takes the per-layer launches.
+bool take_tower_give_up(cattus_eval* e, Lane& L) {
+    if (!L.h_tower_err.p || *L.h_tower_err.as<volatile unsigned>() == 0) return false;
+    *L.h_tower_err.as<volatile unsigned>() = 0;
+    e->tower_gave_up.store(true, std::memory_order_relaxed);
+    std::lock_guard<std::mutex> sl(e->stat_mu);
+    e->stats_tower_fallbacks += 1;
+    return true;
 }
 
 struct LegalArgs {
@@ -1009,23 +882,13 @@ int eval_host(cattus_eval* e, const uint64_t* planes, uint32_t n, float* policy,
     };
     int rc = run_batch();
     if (rc) return rc;
-    if (L.h_tower_err.p && *L.h_tower_err.as<volatile unsigned>() != 0) {
-        // a hand-off wait of the one-launch tower ran out of its budget (its workgroups were not all resident: somebody else's kernels
-        // on this device): the launch finished on rows that were not ready.  Nothing of it is kept: this evaluator goes back to the
-        // per-layer launches, for this batch (again, from the planes) and for every later one.
-        *L.h_tower_err.as<volatile unsigned>() = 0;
-        e->persist_ok.store(false, std::memory_order_relaxed);
-        {
-            std::lock_guard<std::mutex> sl(e->stat_mu);
-            e->stats_tower_fallbacks += 1;
-        }
-        if ((rc = run_batch())) return rc;
-    }
+    if (take_tower_give_up(e, L) && (rc = run_batch())) return rc;  // this batch again, from the planes, on the per-layer launches
     if (!direct) {
         if (!lg) memcpy(policy, L.h_policy.p, (size_t)n * d.moves * 4);
         memcpy(value, L.h_value.p, (size_t)n * 4);
     }
-    account(e, n, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    account(e, n, &seconds);
     return CATTUS_OK;
 }
 
@@ -1092,12 +955,16 @@ CATTUS_API const char* cattus_hip_runtime_note(void) { return g_runtime_note.c_s
 
 CATTUS_API const char* cattus_hip_tower_kernel(const cattus_eval* e) {
     if (!e) return "";
-    if (e->simple) return "policy_fc_kernel";
-    if (!e->tuned) return "conv3x3_generic_kernel";
-    if (e->tower64) return "tower64_lds_kernel";
-    if (e->tower64s) return "tower64_split_kernel";
-    if (e->act == Act::F16S) return e->d.blocks > 0 && e->c1[0]->wu.p ? (e->wino_k4 ? (e->lanes[0].tower_nlayers && e->persist_ok.load() && wino4_tower_fits(e->bpad, e->fpad, e->cus) ? "tower_wino4_kernel" : "conv3x3_wino4_kernel") : "conv3x3_wino_kernel") : e->split_wfrag ? "conv3x3_splitw_kernel" : "conv3x3_split_kernel";
-    return "conv3x3_mfma_v2_kernel";
+    switch (e->plan.kind) {
+        case TowerKind::Simple: return "policy_fc_kernel";
+        case TowerKind::Generic: return "conv3x3_generic_kernel";
+        case TowerKind::Resident64: return "tower64_lds_kernel";
+        case TowerKind::Resident64Split: return "tower64_split_kernel";
+        case TowerKind::Wino16: return "conv3x3_wino_kernel";
+        case TowerKind::Wino4: return one_launch_now(e, e->bpad) ? "tower_wino4_kernel" : "conv3x3_wino4_kernel";
+        case TowerKind::PerLayer: break;
+    }
+    return e->act != Act::F16S ? "conv3x3_mfma_v2_kernel" : e->plan.w_frag ? "conv3x3_splitw_kernel" : "conv3x3_split_kernel";
 }
 
 CATTUS_API int cattus_hip_stream_shift(const cattus_eval* e) { return e ? e->stream_shift : 0; }
@@ -1135,7 +1002,42 @@ struct Switches {
         auto it = kv.find(key);
         return it == kv.end() ? nullptr : it->second.c_str();
     }
+    bool starts(const char* key, char c) const { return get(key) && get(key)[0] == c; }  // the switch is given and its value begins with c
+    int number(const char* key) const { return get(key) ? atoi(get(key)) : 0; }          // 0 when the switch is not given
 };
+
+// Which tower runs, from the network, the configuration, the switches and the tuned towers' padding (bpad boards, fpad filters, cpad0 stem
+// input channels).  The form is part of the configuration: AUTO = Winograd for max_batch > 128 where a kernel covers the shape; WINOGRAD
+// where none does is refused.  The resident kinds and the Winograd kinds cannot both hold -- the resident kinds need fpad == 64,
+// wino_supported needs cout % 128 == 0 and wino4_supported cout >= 128 -- so the order of the cases below decides nothing between them.
+int resolve_plan(const cattus_net_desc& d, const cattus_eval_config& cfg, const Switches& sw, Act act, uint32_t bpad, uint32_t fpad, uint32_t cpad0,
+                 TowerPlan* plan) {
+    // The MFMA tower covers every board up to 11x11 and any filter count (channels are padded to 64 with zeros);
+    // the two 1x1 head convs share one 32-row MFMA tile.  Wider heads take the generic f32 path (one thread
+    // per output, same arithmetic order), which otherwise serves as a checker only (CATTUS_FORCE_GENERIC=1).
+    const bool simple = d.filters == 0, tuned = !simple && d.vhc + d.phc <= 32 && !sw.starts("CATTUS_FORCE_GENERIC", '1');
+    if (!tuned && act != Act::F32)
+        return fail(CATTUS_E_UNSUPPORTED, "bf16 / f16 / f16x2 need the MFMA tower: value + policy head channels <= 32 (got %u + %u)", d.vhc, d.phc);
+    // the 4-frequency kernel wherever it covers the layer shape (filters a multiple of 64), else the 16-frequency one (128)
+    const char* wk = sw.get("CATTUS_WINO_KERNEL");
+    if (wk && strcmp(wk, "k16") != 0 && strcmp(wk, "k4") != 0) return fail(CATTUS_E_INVALID, "CATTUS_WINO_KERNEL is k16 or k4");
+    const bool k4 = wk ? strcmp(wk, "k4") == 0 : wino4_supported(bpad, fpad, fpad, d.board);
+    const bool wino_covers = tuned && act == Act::F16S && d.blocks > 0 && (k4 ? wino4_supported : wino_supported)(bpad, fpad, fpad, d.board);
+    if (cfg.tower_form == CATTUS_TOWER_WINOGRAD && !wino_covers)
+        return fail(CATTUS_E_UNSUPPORTED, "tower_form WINOGRAD needs dtype f16x2, an 8x8 board, at least one residual block and a multiple of 64 filters");
+    TowerPlan& p = *plan = TowerPlan();
+    p.w_frag = tuned && act == Act::F16S && !sw.starts("CATTUS_SPLIT_W", '0');
+    const bool resident = tuned && fpad == 64 && !sw.starts("CATTUS_TOWER64", '0');
+    if (!tuned) p.kind = simple ? TowerKind::Simple : TowerKind::Generic;
+    else if (wino_covers && (cfg.tower_form == CATTUS_TOWER_WINOGRAD || (cfg.tower_form == CATTUS_TOWER_AUTO && cfg.max_batch > 128))) {
+        p.kind = k4 ? TowerKind::Wino4 : TowerKind::Wino16;
+        p.inplace = !sw.starts("CATTUS_WINO_INPLACE", '0');
+        p.one_launch = k4 && p.inplace && !sw.starts("CATTUS_WINO_PERSIST", '0');
+    } else if (resident && act == Act::BF16 && cpad0 == 64) p.kind = TowerKind::Resident64;
+    else if (resident && act == Act::F16S && cpad0 == 32 && p.w_frag && 1 + 2 * d.blocks <= (uint32_t)T64S_MAX_LAYERS) p.kind = TowerKind::Resident64Split;
+    else p.kind = TowerKind::PerLayer;
+    return CATTUS_OK;
+}
 
 int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cfg_in, const char* switches, cattus_eval** out) {
     if (!out) return fail(CATTUS_E_INVALID, "out is NULL");
@@ -1197,99 +1099,58 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
                                               "export HIP_FORCE_DEV_KERNARG=1 before the process initialises HIP";
     }
     const char* wait_mode = getenv("CATTUS_HIP_WAIT");  // operational, not A/B: how the host thread waits for a batch
-    const char* conv_cb_env = sw.get("CATTUS_CONV_CB");
-    const char* conv_pbw_env = sw.get("CATTUS_CONV_PBW");
-    const char* fused_stem_env = sw.get("CATTUS_FUSED_STEM");
-    const char* t64_ch_env = sw.get("CATTUS_T64_CH");
-    const char* t64_ls_env = sw.get("CATTUS_T64_LS");
-    const char* split_w_env = sw.get("CATTUS_SPLIT_W");
-    const char* t64s_heads_env = sw.get("CATTUS_T64S_HEADS");
-    const char* t64s_d_env = sw.get("CATTUS_T64S_SHAPE");
-    const char* tower64_env = sw.get("CATTUS_TOWER64");
-    const char* stream_shift_env = sw.get("CATTUS_STREAM_SHIFT");
 
     std::unique_ptr<cattus_eval> e(new (std::nothrow) cattus_eval);
     if (!e) return fail(CATTUS_E_NOMEM, "out of memory");
-    e->d = d;
-    e->cfg = *cfg;
+    e->d = d, e->cfg = *cfg;
     if (e->cfg.flush_us == 0) e->cfg.flush_us = 200;
     e->device = cfg->device;
     e->wait_spin = !(wait_mode && strcmp(wait_mode, "block") == 0);
-    e->pack_separately = fused_stem_env && fused_stem_env[0] == '0';
-    e->t64_force_ch = t64_ch_env ? atoi(t64_ch_env) : 0;
-    e->t64_layer_steps = !(t64_ls_env && atoi(t64_ls_env) == 0);
-    e->split_wfrag = !(split_w_env && split_w_env[0] == '0');
-    e->stream_shift_on = !(stream_shift_env && stream_shift_env[0] == '0');
-    // the tower's form is part of the configuration (a leaf's bits must not depend on the batch it came in, so never per batch):
-    // AUTO = Winograd for max_batch > 128 where the shape allows it; WINOGRAD on a shape it does not cover is refused below
-    e->winograd = cfg->tower_form == CATTUS_TOWER_WINOGRAD || (cfg->tower_form == CATTUS_TOWER_AUTO && cfg->max_batch > 128);
-    e->resident_tower = !(tower64_env && tower64_env[0] == '0');
-    e->t64s_fuse_heads = !(t64s_heads_env && t64s_heads_env[0] == '0');
-    e->t64s_depth = t64s_d_env ? atoi(t64s_d_env) : 0;
-    e->conv_opts.cb = conv_cb_env ? atoi(conv_cb_env) : 0;
-    e->conv_opts.pbw = conv_pbw_env ? atoi(conv_pbw_env) : 0;
+    e->pack_separately = sw.starts("CATTUS_FUSED_STEM", '0');
+    e->t64_force_ch = sw.number("CATTUS_T64_CH");
+    e->t64_layer_steps = !(sw.get("CATTUS_T64_LS") && sw.number("CATTUS_T64_LS") == 0);
+    e->stream_shift_on = !sw.starts("CATTUS_STREAM_SHIFT", '0');
+    e->t64s_fuse_heads = !sw.starts("CATTUS_T64S_HEADS", '0');
+    e->t64s_depth = sw.number("CATTUS_T64S_SHAPE");
+    e->conv_opts.cb = sw.number("CATTUS_CONV_CB");
+    e->conv_opts.pbw = sw.number("CATTUS_CONV_PBW");
     e->hw = d.board * d.board;
-    // The MFMA tower covers every board up to 11x11 and any filter count (channels are padded to 64 with zeros);
-    // the two 1x1 head convs share one 32-row MFMA tile.  Wider heads take the generic f32 path (one thread
-    // per output, same arithmetic order), which otherwise serves as a checker only (CATTUS_FORCE_GENERIC=1).
-    const char* force_generic = sw.get("CATTUS_FORCE_GENERIC");
-    e->simple = simple;
-    e->tuned = !simple && d.vhc + d.phc <= 32 && !(force_generic && force_generic[0] == '1');
     e->act = simple ? Act::F32
              : cfg->dtype == CATTUS_DTYPE_BF16 ? Act::BF16
              : cfg->dtype == CATTUS_DTYPE_F16X2 ? Act::F16S
              : cfg->dtype == CATTUS_DTYPE_F16 ? Act::F16
                                               : Act::F32;
-    if (!e->tuned && e->act != Act::F32)
-        return fail(CATTUS_E_UNSUPPORTED, "bf16 / f16 / f16x2 need the MFMA tower: value + policy head channels <= 32 (got %u + %u)", d.vhc, d.phc);
+    // the f16 towers' stems expand the planes themselves (no separate plane pack exists for them)
+    if (act_f16_family(e->act) && d.planes > 32) return fail(CATTUS_E_UNSUPPORTED, "f16x2 / f16 take at most 32 input planes (got %u)", d.planes);
+    // the tuned towers' layout: whole workgroups of boards, filters in whole 64-channel groups (zero channels), the planes in whole
+    // 128-byte rows; the other towers pad nothing
+    e->slots = tower_slots(d.board);
+    const uint32_t bpw = ROWS_PER_WG / e->slots, kc = (uint32_t)act_kc(e->act);
+    e->bpad = (cfg->max_batch + bpw - 1) / bpw * bpw, e->cpad0 = (d.planes + kc - 1) / kc * kc;
+    e->fpad = (d.filters + COUT_PER_WG - 1) / COUT_PER_WG * COUT_PER_WG;
+    if (int prc = resolve_plan(d, *cfg, sw, e->act, e->bpad, e->fpad, e->cpad0, &e->plan)) return prc;
+    if (!e->plan.tuned()) e->bpad = cfg->max_batch, e->fpad = d.filters, e->cpad0 = d.planes;
     if (act_f16_family(e->act)) {
-        int src = e->d_saturated.alloc(sizeof(unsigned));
-        if (src) return src;
+        e->pack_separately = false;  // their stems expand the planes themselves
+        if (int src = e->d_saturated.alloc(sizeof(unsigned))) return src;
         HIP_TRY(hipMemset(e->d_saturated.p, 0, sizeof(unsigned)));
         e->conv_opts.saturated = e->d_saturated.as<unsigned>();
     }
-    if (act_f16_family(e->act)) {
-        // the f16 towers' stems expand the planes themselves (no separate plane pack exists for them)
-        if (d.planes > 32) return fail(CATTUS_E_UNSUPPORTED, "f16x2 / f16 take at most 32 input planes (got %u)", d.planes);
-        e->pack_separately = false;
-    }
-    e->slots = tower_slots(d.board);
-    e->fpad = e->tuned ? (d.filters + COUT_PER_WG - 1) / COUT_PER_WG * COUT_PER_WG : d.filters;
-    const uint32_t bpw = e->tuned ? ROWS_PER_WG / e->slots : 1;
-    e->bpad = (cfg->max_batch + bpw - 1) / bpw * bpw;
-    const char* inplace_env = sw.get("CATTUS_WINO_INPLACE");
-    e->wino_inplace = !(inplace_env && inplace_env[0] == '0');
-    const char* arena_env = sw.get("CATTUS_ARENA");  // 0: every buffer its own allocation (A/B runs)
-    {
-        // the 4-frequency kernel wherever it covers the layer shape (filters a multiple of 64), else the 16-frequency one (128)
-        const char* wk = sw.get("CATTUS_WINO_KERNEL");
-        if (wk && strcmp(wk, "k16") != 0 && strcmp(wk, "k4") != 0) return fail(CATTUS_E_INVALID, "CATTUS_WINO_KERNEL is k16 or k4");
-        e->wino_k4 = wk ? strcmp(wk, "k4") == 0 : wino4_supported(e->bpad, e->fpad, e->fpad, d.board);
-    }
-    {
-        const char* wp = sw.get("CATTUS_WINO_PERSIST");
-        e->wino_persist = !(wp && wp[0] == '0');
-        const char* ws = sw.get("CATTUS_WINO_SPIN");
-        if (ws) e->persist_spin = (uint32_t)std::max(1L, atol(ws));
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, cfg->device));
-        e->cus = (uint32_t)prop.multiProcessorCount;
-    }
-    if (cfg->tower_form == CATTUS_TOWER_WINOGRAD && !(e->tuned && e->act == Act::F16S && d.blocks > 0 && wino_shape_ok(e.get(), e->fpad, e->fpad)))
-        return fail(CATTUS_E_UNSUPPORTED, "tower_form WINOGRAD needs dtype f16x2, an 8x8 board, at least one residual block and a multiple of 64 filters");
-    if (e->tuned && e->act == Act::F16S && e->winograd && d.blocks > 0 && wino_shape_ok(e.get(), e->fpad, e->fpad) &&
-        !(arena_env && arena_env[0] == '0')) {
+    if (const char* ws = sw.get("CATTUS_WINO_SPIN")) e->persist_spin = (uint32_t)std::max(1L, atol(ws));
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, cfg->device));
+    e->cus = (uint32_t)prop.multiProcessorCount;
+    if (e->plan.wino() && !sw.starts("CATTUS_ARENA", '0')) {  // CATTUS_ARENA=0: every buffer its own allocation (A/B runs)
         // the Winograd tower's hot set in one block: U of every layer, then the lanes' activation buffers (DevArena)
         auto page = [](size_t b) { return (b + 4095) & ~(size_t)4095; };
         const size_t FPz = e->fpad, u_bytes = page(((size_t)16 * FPz * FPz * 2 + (size_t)WINO_RING_STAGES * 1024) * 2);
         const size_t act_bytes_ = page((size_t)e->bpad * e->slots * FPz * 4);
-        const size_t want = 2 * (size_t)d.blocks * u_bytes + (size_t)NLANES * (e->wino_inplace ? 2 : 3) * act_bytes_ + (1u << 20);
+        const size_t want = 2 * (size_t)d.blocks * u_bytes + (size_t)NLANES * (e->plan.inplace ? 2 : 3) * act_bytes_ + (1u << 20);
         void* base = nullptr;
         if (hipMalloc(&base, want) == hipSuccess) e->arena.base = (char*)base, e->arena.cap = want;
         else (void)hipGetLastError();  // no room for one block: separate allocations, as before
     }
-    int rc = build(e.get(), reinterpret_cast<const float*>((const char*)weights + HEADER_BYTES));
-    if (rc) return rc;
+    if (int rc = build(e.get(), reinterpret_cast<const float*>((const char*)weights + HEADER_BYTES))) return rc;
     HIP_TRY(hipDeviceSynchronize());
     {
         std::lock_guard<std::mutex> lk(e->srv_mu);
@@ -1353,20 +1214,13 @@ CATTUS_API int cattus_hip_eval_device_lane(cattus_eval* e, uint32_t lane, const 
     Lane& L = e->lanes[lane];
     std::lock_guard<std::mutex> lk(L.mu);
     HIP_TRY(hipSetDevice(e->device));
-    if (L.h_tower_err.p && *L.h_tower_err.as<volatile unsigned>() != 0) {
-        // this entry point is asynchronous: what an earlier call's one-launch tower reported is seen here, at the next call
-        *L.h_tower_err.as<volatile unsigned>() = 0;
-        e->persist_ok.store(false, std::memory_order_relaxed);
+    if (take_tower_give_up(e, L))  // this entry point is asynchronous: what an earlier call's one-launch tower reported is seen here, at the next call
         return fail(CATTUS_E_DEVICE, "an earlier batch on lane %u ran the tower as one launch and a hand-off wait in it gave up (the device was shared): that batch's "
                                      "outputs are invalid; this evaluator uses the per-layer launches from now on", lane);
-    }
     hipStream_t st = (hipStream_t)stream;  // as HIP itself: NULL is the legacy default stream, not a private one
     int rc = enqueue_forward(e, L, d_planes, n, d_policy, d_value, st);
     if (rc) return rc;
-    std::lock_guard<std::mutex> sl(e->stat_mu);
-    e->stats.batches += 1;
-    e->stats.positions += n;
-    if (n == e->cfg.max_batch) e->stats.full_batches += 1;
+    account(e, n, nullptr);
     return CATTUS_OK;
 }
 
@@ -1499,13 +1353,13 @@ CATTUS_API int cattus_hip_stats(cattus_eval* e, cattus_stats* out) {
 CATTUS_API int cattus_hip_time_tower(cattus_eval* e, uint32_t n, uint32_t reps, float* avg_launch_us, uint32_t* launches) {
     if (!e || !avg_launch_us || !launches) return fail(CATTUS_E_INVALID, "NULL argument");
     if (n < 1 || n > e->cfg.max_batch || reps < 1) return fail(CATTUS_E_INVALID, "bad n/reps");
-    if (e->simple) return fail(CATTUS_E_UNSUPPORTED, "a SimpleTwoHeadedModel has no conv tower to time");
+    if (e->plan.kind == TowerKind::Simple) return fail(CATTUS_E_UNSUPPORTED, "a SimpleTwoHeadedModel has no conv tower to time");
     Lane& L = e->lanes[0];
     std::lock_guard<std::mutex> lk(L.mu);
     HIP_TRY(hipSetDevice(e->device));
     // (the one-launch Winograd tower is reported per LAYER: its duration + the stem's over 1 + 2 blocks, so that a caller's
     // flops-per-launch arithmetic does not change with how the layers are launched)
-    const uint32_t per_fwd = e->tower64 || e->tower64s ? 1 : 1 + 2 * e->d.blocks;
+    const uint32_t per_fwd = e->plan.kind == TowerKind::Resident64 || e->plan.kind == TowerKind::Resident64Split ? 1 : 1 + 2 * e->d.blocks;
     TowerTimer tt;
     tt.ev.resize((size_t)2 * per_fwd);
     for (auto& ev : tt.ev) HIP_TRY(hipEventCreate(&ev));

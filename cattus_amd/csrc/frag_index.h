@@ -1,0 +1,23 @@
+// Where a weight lives in the fragment-ordered buffers of the f16x2 kernels (kernels.h): shared by the host code that writes them
+// (weight_layout.h) and the kernels' interface.  Plain C++, no HIP.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace cattus {
+
+// CONV_W_FRAG: element index of weight (tap t, output channel co, input channel ci, part 0 = hi / 1 = lo)
+inline size_t split_frag_index(uint32_t t, uint32_t co, uint32_t ci, uint32_t part, uint32_t cin_pad) {
+    const uint32_t nst = cin_pad / 32 * 18, ch = ci >> 5, k = (ci >> 4) & 1, h = (ci >> 3) & 1, e = ci & 7;
+    const uint32_t stage = ((ch * 3 + t / 3) * 3 + t % 3) * 2 + k, lane = h * 32 + (co & 31);
+    return ((((size_t)(co >> 5) * nst + stage) * 2 + part) * 64 + lane) * 8 + e;
+}
+// K1w / K1w4: element index of U (frequency f, output channel co, input channel ci, part); the kernels' weight ring reads
+// WINO_RING_STAGES stages (of 2,048 B) past a cout block's end: wu is allocated with that much behind it
+constexpr int WINO_RING_STAGES = 8;
+inline size_t wino_frag_index(uint32_t f, uint32_t co, uint32_t ci, uint32_t part, uint32_t cin_pad) {
+    const uint32_t nst = cin_pad / 16 * 16, stage = (ci >> 4) * 16 + f, lane = ((ci >> 3) & 1) * 32 + (co & 31);
+    return ((((size_t)(co >> 5) * nst + stage) * 2 + part) * 64 + lane) * 8 + (ci & 7);
+}
+
+}  // namespace cattus

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "frag_index.h"  // split_frag_index, wino_frag_index, WINO_RING_STAGES
+
 namespace cattus {
 
 // Tower layout: a board owns 64 pixel slots (board edge <= 8) or 128 (edge 9..11); rows = board * slots + slot.
@@ -55,19 +57,13 @@ struct StemInput {
 // [cout biases | cout inverse scales].
 // flags & CONV_OUT_F32 (F16S / F16 only): out is written as plain f32 [row][cout] (last tower layer, read by the f32 head kernels).
 // flags & CONV_W_FRAG (F16S only): w is in MFMA fragment order, [cout / 32][stage][hi | lo][lane][8 f16] with
-// stage = ((chunk * 3 + dy) * 3 + dx) * 2 + k-half (split_frag_index below): the kernel that keeps the weights in a register
+// stage = ((chunk * 3 + dy) * 3 + dx) * 2 + k-half (split_frag_index): the kernel that keeps the weights in a register
 // ring instead of LDS.  Non-stem layers then need cin >= 64.
 // flags & CONV_WINO_IN (with CONV_OUT_F32): the rows feed a Winograd tower (K1w): values are capped at WINO_ACT_MAX and counted in
 // `sat` beyond it -- a transformed input B^T d B is a signed sum of four activations, so no |V| can leave the f16 range then and the
 // Winograd kernel's transform needs neither a clamp nor a range check of its own.
 constexpr int CONV_OUT_F32 = 1, CONV_W_FRAG = 2, CONV_WINO_IN = 4;
 constexpr float WINO_ACT_MAX = 16376.0f;  // 65504 / 4, exactly
-// Element index of weight (tap t, output channel co, input channel ci, part 0 = hi / 1 = lo) in fragment order.
-inline size_t split_frag_index(uint32_t t, uint32_t co, uint32_t ci, uint32_t part, uint32_t cin_pad) {
-    const uint32_t nst = cin_pad / 32 * 18, ch = ci >> 5, k = (ci >> 4) & 1, h = (ci >> 3) & 1, e = ci & 7;
-    const uint32_t stage = ((ch * 3 + t / 3) * 3 + t % 3) * 2 + k, lane = h * 32 + (co & 31);
-    return ((((size_t)(co >> 5) * nst + stage) * 2 + part) * 64 + lane) * 8 + e;
-}
 // Per-evaluator launch options (they used to be process-wide switches: a second evaluator must not re-tile the first).
 struct ConvOpts {
     int cb = 0;   // forces the conv kernel's tile: 1 = 256 rows x 32 couts, 2 = 256 rows x 64 couts; 0 = chosen by grid size
@@ -86,14 +82,8 @@ void launch_conv3x3_mfma(Act act, const void* in, const void* w, const float* bi
 // activations between its layers); wu = G g G^T as (hi, lo) f16 pairs pre-scaled per output channel, in fragment order
 // [cout / 32][(cin / 16) k-steps x 16 frequencies][hi | lo][lane][8 f16] (wino_frag_index); bias = [cout biases | cout inverse
 // scales] of THAT scaling; res may be out (a block's output over its skip rows); outputs are capped at WINO_ACT_MAX and sat counts
-// the threads that wrote the cap.
-// the kernel's weight ring reads WINO_RING_STAGES stages (of 2,048 B) past a cout block's end: wu is allocated with that much behind it
-constexpr int WINO_RING_STAGES = 8;
+// the threads that wrote the cap.  The kernel's weight ring reads WINO_RING_STAGES stages past a cout block's end (frag_index.h).
 bool wino_supported(uint32_t bpad, uint32_t cin, uint32_t cout, uint32_t S);
-inline size_t wino_frag_index(uint32_t f, uint32_t co, uint32_t ci, uint32_t part, uint32_t cin_pad) {
-    const uint32_t nst = cin_pad / 16 * 16, stage = (ci >> 4) * 16 + f, lane = ((ci >> 3) & 1) * 32 + (co & 31);
-    return ((((size_t)(co >> 5) * nst + stage) * 2 + part) * 64 + lane) * 8 + (ci & 7);
-}
 void launch_conv3x3_wino(const float* in, const void* wu, const float* bias, const float* res, float* out, uint32_t bpad, uint32_t cin,
                          uint32_t cout, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, unsigned* sat);
 hipError_t prepare_wino();  // its dynamic-LDS opt-in; called by prepare_device()

@@ -1,0 +1,130 @@
+// The device layouts of one folded 3x3 conv layer, as host vectors: pure functions of the layer and its padded shape -- no HIP call,
+// nothing of the evaluator -- so that every index can be checked without a GPU (tests/test_weight_layout.py).  Output channels are
+// padded to cout_pad and input channels to the device layout of the producing layer (cin_pad, a multiple of one 128-byte row) with
+// zero weights and zero bias: a padded channel computes relu(0) = 0, and as an input it adds fmaf(0, x, acc) = acc terms only, so the
+// f32 chains of the real channels are bit for bit unchanged.  Compiled with -ffp-contract=off like all host code here.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "frag_index.h"
+
+namespace cattus {
+
+struct Folded {
+    std::vector<float> w;  // [taps][cout][cin]
+    std::vector<float> b;  // [cout]
+};
+struct ConvShape { uint32_t cout, cin, cout_pad, cin_pad; };  // of the Folded layer; as laid out on the device
+
+inline uint16_t f32_to_bf16(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // keep NaN a NaN
+    u += 0x7fffu + ((u >> 16) & 1u);                                           // round to nearest even
+    return (uint16_t)(u >> 16);
+}
+
+// The f16 towers' power-of-two scale 2^s of one output channel: its largest |w 2^s| lies in [2^10, 2^11), so the lo halves of all but
+// the channel's tiniest weights are normal f16 numbers (22 significant bits per weight; single-term f16: no weight becomes a
+// subnormal unless it is 2^-24 of the largest) and nothing comes near the f16 range limit.  2^-s -- applied to the f32 accumulator
+// in the epilogue -- undoes the scale exactly.
+inline int channel_shift(double max_abs) { return max_abs > 0.0 && std::isfinite(max_abs) ? std::min(100, std::max(-100, 10 - ilogb(max_abs))) : 0; }
+
+// [cout_pad biases | cout_pad inverse scales 2^-shift]; without shifts (f32, bf16) the biases alone
+inline std::vector<float> bias_and_scales(const Folded& f, const ConvShape& s, const std::vector<int>* shift = nullptr) {
+    std::vector<float> b((size_t)(shift ? 2 : 1) * s.cout_pad, 0.0f);
+    memcpy(b.data(), f.b.data(), s.cout * sizeof(float));
+    for (uint32_t co = 0; shift && co < s.cout_pad; co++) b[s.cout_pad + co] = ldexpf(1.0f, -(*shift)[co]);
+    return b;
+}
+
+// fn(t, co, ci, w) for every weight of the layer
+template <class Fn>
+void for_each_weight(const Folded& f, const ConvShape& s, Fn fn) {
+    for (uint32_t t = 0; t < 9; t++)
+        for (uint32_t co = 0; co < s.cout; co++)
+            for (uint32_t ci = 0; ci < s.cin; ci++) fn(t, co, ci, f.w[((size_t)t * s.cout + co) * s.cin + ci]);
+}
+
+// channel_shift of every output channel over its 9 x cin weights (padded channels: 0)
+inline std::vector<int> channel_shifts(const Folded& f, const ConvShape& s) {
+    std::vector<float> m(s.cout_pad, 0.0f);
+    for_each_weight(f, s, [&](uint32_t, uint32_t co, uint32_t, float w) { m[co] = std::max(m[co], fabsf(w)); });
+    std::vector<int> sh(s.cout_pad);
+    for (uint32_t co = 0; co < s.cout_pad; co++) sh[co] = channel_shift(m[co]);
+    return sh;
+}
+
+// rows [9][cout_pad][cin_pad] of cvt(w, co)
+template <class T, class Cvt>
+std::vector<T> rows(const Folded& f, const ConvShape& s, Cvt cvt) {
+    std::vector<T> w((size_t)9 * s.cout_pad * s.cin_pad, (T)0);
+    for_each_weight(f, s, [&](uint32_t t, uint32_t co, uint32_t ci, float x) { w[((size_t)t * s.cout_pad + co) * s.cin_pad + ci] = cvt(x, co); });
+    return w;
+}
+inline std::vector<float> rows_f32(const Folded& f, const ConvShape& s) { return rows<float>(f, s, [](float x, uint32_t) { return x; }); }
+inline std::vector<uint16_t> rows_bf16(const Folded& f, const ConvShape& s) { return rows<uint16_t>(f, s, [](float x, uint32_t) { return f32_to_bf16(x); }); }
+inline std::vector<_Float16> rows_f16(const Folded& f, const ConvShape& s, const std::vector<int>& shift) {  // single-term f16: f16(w 2^s)
+    return rows<_Float16>(f, s, [&](float x, uint32_t co) { return (_Float16)ldexpf(x, shift[co]); });
+}
+
+// split precision: x as hi = f16(x), lo = f16(x - hi)
+inline void split_f16(float x, _Float16& hi, _Float16& lo) { hi = (_Float16)x, lo = (_Float16)(x - (float)hi); }
+// f16x2: the pair of w 2^s at at(t, co, ci, part 0 = hi / 1 = lo)
+template <class Index>
+std::vector<_Float16> split_weights(const Folded& f, const ConvShape& s, const std::vector<int>& shift, Index at) {
+    std::vector<_Float16> w((size_t)9 * s.cout_pad * 2 * s.cin_pad, (_Float16)0.0f);
+    for_each_weight(f, s, [&](uint32_t t, uint32_t co, uint32_t ci, float x) { split_f16(ldexpf(x, shift[co]), w[at(t, co, ci, 0)], w[at(t, co, ci, 1)]); });
+    return w;
+}
+// rows [9][cout_pad][2 cin_pad]: [hi of 32 input channels | lo of the same 32] per 128 bytes (the LDS-ring kernel)
+inline std::vector<_Float16> rows_f16x2(const Folded& f, const ConvShape& s, const std::vector<int>& shift) {
+    return split_weights(f, s, shift, [&](uint32_t t, uint32_t co, uint32_t ci, uint32_t part) {
+        return ((size_t)t * s.cout_pad + co) * 2 * s.cin_pad + (size_t)(ci >> 5) * 64 + (ci & 31) + 32 * part;
+    });
+}
+// MFMA fragment order (CONV_W_FRAG, the register-ring kernels): a permutation of those rows
+inline std::vector<_Float16> frag_f16x2(const Folded& f, const ConvShape& s, const std::vector<int>& shift) {
+    return split_weights(f, s, shift, [&](uint32_t t, uint32_t co, uint32_t ci, uint32_t part) { return split_frag_index(t, co, ci, part, s.cin_pad); });
+}
+
+// Winograd F(2x2, 3x3) form: U = G g G^T per (cout, cin) in float64, [(co * cin + ci) * 16 + frequency], and one scale per output
+// channel over all 16 frequencies of all its input channels
+inline std::vector<double> wino_transform(const Folded& f, const ConvShape& s, std::vector<int>* shift) {
+    static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+    std::vector<double> U((size_t)s.cout * s.cin * 16);
+    shift->assign(s.cout_pad, 0);
+    for (uint32_t co = 0; co < s.cout; co++) {
+        double m = 0.0;
+        for (uint32_t ci = 0; ci < s.cin; ci++) {
+            double g[3][3], t[4][3];
+            for (int ky = 0; ky < 3; ky++)
+                for (int kx = 0; kx < 3; kx++) g[ky][kx] = f.w[((size_t)(ky * 3 + kx) * s.cout + co) * s.cin + ci];
+            for (int i = 0; i < 4; i++)
+                for (int kx = 0; kx < 3; kx++) t[i][kx] = G[i][0] * g[0][kx] + G[i][1] * g[1][kx] + G[i][2] * g[2][kx];
+            for (int i = 0; i < 4; i++)
+                for (int l = 0; l < 4; l++) {
+                    const double u = t[i][0] * G[l][0] + t[i][1] * G[l][1] + t[i][2] * G[l][2];
+                    U[((size_t)co * s.cin + ci) * 16 + i * 4 + l] = u;
+                    m = std::max(m, fabs(u));
+                }
+        }
+        (*shift)[co] = channel_shift(m);
+    }
+    return U;
+}
+// U 2^s as (hi, lo) pairs in the Winograd kernels' fragment order, with the stages their weight ring reads past the end
+inline std::vector<_Float16> wino_u(const std::vector<double>& U, const ConvShape& s, const std::vector<int>& shift) {
+    std::vector<_Float16> wu((size_t)16 * s.cout_pad * s.cin_pad * 2 + (size_t)WINO_RING_STAGES * 1024, (_Float16)0.0f);
+    for (uint32_t co = 0; co < s.cout; co++)
+        for (uint32_t ci = 0; ci < s.cin; ci++)
+            for (uint32_t q = 0; q < 16; q++)
+                split_f16((float)ldexp(U[((size_t)co * s.cin + ci) * 16 + q], shift[co]), wu[wino_frag_index(q, co, ci, 0, s.cin_pad)], wu[wino_frag_index(q, co, ci, 1, s.cin_pad)]);
+    return wu;
+}
+
+}  // namespace cattus
