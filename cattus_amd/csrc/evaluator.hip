@@ -316,7 +316,7 @@ struct cattus_eval {
     DevBuf t64_layers, t64s_bias;  // the resident towers' layer table; Resident64Split: every layer's [biases | inverse scales]
     bool t64s_fuse_heads = true;  // CATTUS_T64S_HEADS=0: the head convs as their own launch on the tower's f32 rows (A/B, the equality test)
     int t64s_depth = 0;           // CATTUS_T64S_SHAPE=1|2: workgroup shape of the resident split tower (kernels.h; 0: by grid size)
-    bool pack_separately = false;  // CATTUS_FUSED_STEM=0: plane pack as its own launch in front of the stem (A/B, tests)
+    bool pack_separately = false;  // more than 32 planes, or CATTUS_FUSED_STEM=0 (A/B, tests): the plane pack as its own launch in front of the stem
     int t64_force_ch = 0;          // CATTUS_T64_CH=2|4: workgroup shape of the resident tower (A/B runs, the row-split test)
     // the one-launch Winograd tower: set when a launch reported a hand-off wait that gave up (CATTUS_WINO_SPIN=<polls>: the budget of a
     // wait) -- that batch is run again on the per-layer launches, and so is every later one
@@ -684,9 +684,9 @@ struct Forward {
     }
 
     // One direct conv layer of the MFMA tower; `stem`: from the planes (the stem conv expands them itself when they fit one 128-byte
-    // chunk -- every game here -- else K0 packs them first)
+    // chunk -- every game here -- else K0 packs them into x0 first and the stem is an ordinary layer of cpad0 input channels)
     void conv_mfma(const ConvLayer& c, const void* in, const void* res, void* out, int flags, bool stem = false) {
-        const bool fused_stem = stem && d.planes <= 32 && e->cpad0 == (uint32_t)act_kc(e->act) && !e->pack_separately;
+        const bool fused_stem = stem && stem_is_fused(d.planes, e->pack_separately);
         const StemInput stem_in{d_planes, n, d.planes, w64};
         if (stem && !fused_stem) launch_pack_planes_nhwc(e->act, d_planes, n, nb, d.planes, w64, S, e->cpad0, L.x0.p, st);
         hipEvent_t s0 = ev(), s1 = ev();
@@ -969,6 +969,14 @@ CATTUS_API const char* cattus_hip_tower_kernel(const cattus_eval* e) {
 
 CATTUS_API int cattus_hip_stream_shift(const cattus_eval* e) { return e ? e->stream_shift : 0; }
 
+CATTUS_API int cattus_hip_stem_input(const cattus_eval* e, uint32_t* channels, uint32_t* packed) {
+    if (!e) return fail(CATTUS_E_INVALID, "NULL argument");
+    if (channels) *channels = e->cpad0;
+    // the towers that go through Forward::conv_mfma; the resident ones expand the planes in their one launch
+    if (packed) *packed = (e->plan.kind == TowerKind::PerLayer || e->plan.wino()) && !stem_is_fused(e->d.planes, e->pack_separately);
+    return CATTUS_OK;
+}
+
 namespace {
 
 // Diagnostic switches of cattus_hip_create_diag (include/cattus_hip_diag.h): "KEY=VALUE;KEY=VALUE".  cattus_hip_create passes none,
@@ -1106,7 +1114,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
     if (e->cfg.flush_us == 0) e->cfg.flush_us = 200;
     e->device = cfg->device;
     e->wait_spin = !(wait_mode && strcmp(wait_mode, "block") == 0);
-    e->pack_separately = sw.starts("CATTUS_FUSED_STEM", '0');
+    e->pack_separately = d.planes > 32 || sw.starts("CATTUS_FUSED_STEM", '0');
     e->t64_force_ch = sw.number("CATTUS_T64_CH");
     e->t64_layer_steps = !(sw.get("CATTUS_T64_LS") && sw.number("CATTUS_T64_LS") == 0);
     e->stream_shift_on = !sw.starts("CATTUS_STREAM_SHIFT", '0');
@@ -1120,18 +1128,16 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
              : cfg->dtype == CATTUS_DTYPE_F16X2 ? Act::F16S
              : cfg->dtype == CATTUS_DTYPE_F16 ? Act::F16
                                               : Act::F32;
-    // the f16 towers' stems expand the planes themselves (no separate plane pack exists for them)
-    if (act_f16_family(e->act) && d.planes > 32) return fail(CATTUS_E_UNSUPPORTED, "f16x2 / f16 take at most 32 input planes (got %u)", d.planes);
     // the tuned towers' layout: whole workgroups of boards, filters in whole 64-channel groups (zero channels), the planes in whole
     // 128-byte rows; the other towers pad nothing
     e->slots = tower_slots(d.board);
-    const uint32_t bpw = ROWS_PER_WG / e->slots, kc = (uint32_t)act_kc(e->act);
-    e->bpad = (cfg->max_batch + bpw - 1) / bpw * bpw, e->cpad0 = (d.planes + kc - 1) / kc * kc;
+    const uint32_t bpw = ROWS_PER_WG / e->slots;
+    e->bpad = (cfg->max_batch + bpw - 1) / bpw * bpw;
+    e->cpad0 = stem_cin_pad(d.planes, (uint32_t)act_kc(e->act), e->act == Act::F16S, e->pack_separately);
     e->fpad = (d.filters + COUT_PER_WG - 1) / COUT_PER_WG * COUT_PER_WG;
     if (int prc = resolve_plan(d, *cfg, sw, e->act, e->bpad, e->fpad, e->cpad0, &e->plan)) return prc;
     if (!e->plan.tuned()) e->bpad = cfg->max_batch, e->fpad = d.filters, e->cpad0 = d.planes;
     if (act_f16_family(e->act)) {
-        e->pack_separately = false;  // their stems expand the planes themselves
         if (int src = e->d_saturated.alloc(sizeof(unsigned))) return src;
         HIP_TRY(hipMemset(e->d_saturated.p, 0, sizeof(unsigned)));
         e->conv_opts.saturated = e->d_saturated.as<unsigned>();

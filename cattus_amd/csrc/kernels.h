@@ -33,7 +33,9 @@ inline bool act_f16_family(Act a) { return a == Act::F16S || a == Act::F16; }
 hipError_t prepare_device();
 
 // ---- K0: bitboard planes -> tensors -------------------------------------------------------
-// NHWC tower input [bpad][slots][cpad] (rows >= n, slots >= S*S and channels >= C are zero).
+// NHWC tower input [bpad][slots][cpad] in the activation layout of `act` -- f32, bf16 or f16 rows, or the F16S pairs (4 bytes per
+// channel, [hi of 32 channels | lo of the same 32] per 128 bytes; hi = f16(bit), lo = 0); rows >= n, slots >= S*S and channels >= C
+// are zero.  C * w64 <= 128 plane words, cpad >= C a multiple of one 128-byte row of the layout.
 void launch_pack_planes_nhwc(Act act, const uint64_t* planes, uint32_t n, uint32_t bpad, uint32_t C,
                              uint32_t w64, uint32_t S, uint32_t cpad, void* out, hipStream_t st);
 // Reference layout: f32 NCHW [batch][C][S*S], rows >= n zero (engine/src/net/mod.rs:121-156).
@@ -45,7 +47,8 @@ void launch_planes_to_tensor_nchw(const uint64_t* planes, uint32_t n, uint32_t C
 // Requires bpad * slots % 256 == 0, cin % kc == 0, cout % 64 == 0, S <= 11.
 // ev_start / ev_stop (optional): events stamped with the kernel's own begin / end time.
 // stem (optional): the layer reads the leaves' bitboard planes instead of `in` (K0 fused into the stem conv: the
-// loader waves expand the planes straight into LDS).  Requires C <= 32 planes and cin == one 128-byte row.
+// loader waves expand the planes straight into LDS).  Requires C <= 32 planes and cin == one 128-byte row; more planes go
+// through launch_pack_planes_nhwc and the layer without `stem` (F16S: cin a multiple of 64 then, see CONV_W_FRAG below).
 struct StemInput {
     const uint64_t* planes;  // [n][C][w64]
     uint32_t n, C, w64;

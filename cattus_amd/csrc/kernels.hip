@@ -1,7 +1,8 @@
 // gfx950 (MI355X / CDNA4) kernels of the Cattus leaf evaluator.
 //
-//   K0  planes_to_tensor_nchw[64] / pack_planes_nhwc    bitboards -> tensors (HBM-bound); inside the forward pass the
-//                                                       planes are expanded straight into LDS by K1 / K1r instead
+//   K0  planes_to_tensor_nchw[64] / pack_planes_nhwc    bitboards -> tensors (HBM-bound); inside the forward pass the planes of a
+//                                                       network of <= 32 planes are expanded straight into LDS by K1 / K1s / K1r
+//                                                       instead, more planes are packed in the tower's own layout (all four)
 //   K1  conv3x3_mfma_v2<T, HAS_RES, BIG, STEM>          3x3 conv + folded BN (+skip) + ReLU, one launch per layer (MFMA-bound), bf16 / f32
 //   K1s conv3x3_splitw<HAS_RES, BIG, STEM, CB>          the same layer of the split-precision tower (dtype f16x2, the default):
 //                                                       operands as pairs of f16 values, three f16 MFMA terms per product;
@@ -37,29 +38,35 @@ namespace cattus {
 
 // One workgroup per board: the board's C*w64 plane words are staged in LDS, then every thread
 // writes 16-byte channel vectors so that a wave stores 1 KiB contiguous.
-template <typename T>
+// PAIRS (T = _Float16): the split-precision tower's rows, 4 bytes per channel -- every 128 bytes are [hi of channels
+// 32g .. 32g+31 | lo of the same 32], i.e. 16-byte vectors 0..3 of a chunk carry hi = f16(bit) of 8 channels each and
+// vectors 4..7 the lo halves, which are zero (a plane bit is 0 or 1).
+template <typename T, bool PAIRS = false>
 __global__ void __launch_bounds__(256) pack_planes_nhwc_kernel(const uint64_t* __restrict__ planes, uint32_t n,
                                                                uint32_t C, uint32_t w64, uint32_t hw, uint32_t cpad,
                                                                uint32_t slots, T* __restrict__ out) {
     constexpr uint32_t VEC = 16 / sizeof(T);
+    static_assert(!PAIRS || sizeof(T) == 2, "pairs are two f16 values");
     __shared__ uint64_t pl[128];
     const uint32_t b = blockIdx.x;
     const uint32_t words = C * w64;
     for (uint32_t i = threadIdx.x; i < words; i += 256) pl[i] = b < n ? planes[(size_t)b * words + i] : 0ull;
     __syncthreads();
-    const uint32_t groups = cpad / VEC;
-    T* ob = out + (size_t)b * slots * cpad;
+    const uint32_t row = (PAIRS ? 2 : 1) * cpad, groups = row / VEC;  // elements / 16-byte vectors of a row
+    T* ob = out + (size_t)b * slots * row;
     for (uint32_t v = threadIdx.x; v < slots * groups; v += 256) {
-        const uint32_t q = v / groups, c0 = (v % groups) * VEC;
+        const uint32_t q = v / groups, j = v % groups;
+        const uint32_t c0 = PAIRS ? (j >> 3) * 32 + (j & 3) * VEC : j * VEC;
+        const bool lo = PAIRS && (j & 4);
         T vals[VEC];
 #pragma unroll
         for (uint32_t i = 0; i < VEC; i++) {
             const uint32_t c = c0 + i;
             uint32_t bit = 0;
-            if (c < C && q < hw) bit = (uint32_t)(pl[c * w64 + (q >> 6)] >> (q & 63)) & 1u;
+            if (!lo && c < C && q < hw) bit = (uint32_t)(pl[c * w64 + (q >> 6)] >> (q & 63)) & 1u;
             vals[i] = bit ? (T)1.0f : (T)0.0f;
         }
-        *reinterpret_cast<f32x4*>(ob + (size_t)q * cpad + c0) = *reinterpret_cast<f32x4*>(vals);
+        *reinterpret_cast<f32x4*>(ob + (size_t)q * row + (size_t)j * VEC) = *reinterpret_cast<f32x4*>(vals);
     }
 }
 
@@ -93,12 +100,19 @@ __global__ void __launch_bounds__(256) planes_to_tensor_nchw_kernel(const uint64
 void launch_pack_planes_nhwc(Act act, const uint64_t* planes, uint32_t n, uint32_t bpad, uint32_t C, uint32_t w64,
                              uint32_t S, uint32_t cpad, void* out, hipStream_t st) {
     const uint32_t slots = tower_slots(S);
-    if (act == Act::BF16)
-        hipLaunchKernelGGL(pack_planes_nhwc_kernel<__bf16>, dim3(bpad), dim3(256), 0, st, planes, n, C, w64, S * S, cpad,
-                           slots, (__bf16*)out);
-    else
-        hipLaunchKernelGGL(pack_planes_nhwc_kernel<float>, dim3(bpad), dim3(256), 0, st, planes, n, C, w64, S * S, cpad,
-                           slots, (float*)out);
+    if (C * w64 > 128 || cpad < C || cpad % 8 != 0) {  // the kernel's LDS stage; whole 16-byte vectors of channels
+        fprintf(stderr, "cattus: launch_pack_planes_nhwc: %u planes x %u words into %u channels\n", C, w64, cpad);
+        abort();
+    }
+    auto launch = [&](auto kernel, auto* o) {
+        hipLaunchKernelGGL(kernel, dim3(bpad), dim3(256), 0, st, planes, n, C, w64, S * S, cpad, slots, o);
+    };
+    switch (act) {
+        case Act::F32: launch(pack_planes_nhwc_kernel<float>, (float*)out); break;
+        case Act::BF16: launch(pack_planes_nhwc_kernel<__bf16>, (__bf16*)out); break;
+        case Act::F16: launch(pack_planes_nhwc_kernel<_Float16>, (_Float16*)out); break;
+        case Act::F16S: launch(pack_planes_nhwc_kernel<_Float16, true>, (_Float16*)out); break;
+    }
 }
 
 // 8x8 boards: one plane = 64 floats = 256 B.  A thread turns one nibble of the plane word into 4 floats

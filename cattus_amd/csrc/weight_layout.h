@@ -20,6 +20,16 @@ struct Folded {
 };
 struct ConvShape { uint32_t cout, cin, cout_pad, cin_pad; };  // of the Folded layer; as laid out on the device
 
+// Input channels of the stem as laid out on the device (cpad0): the planes in whole 128-byte rows of the tower's activation layout,
+// row_channels to a row (kernels.h, act_kc: 32 for f32 and f16x2, 64 for bf16 and f16).  The f16x2 stem that expands the planes itself
+// (STEM, at most 32 planes) runs that one chunk; on packed input it is an ordinary layer of conv3x3_splitw / conv3x3_split, whose loaders
+// request two chunks up front, so its channels are then padded to whole pairs of chunks (64) -- chunk counts the hidden layers run too.
+inline bool stem_is_fused(uint32_t planes, bool pack_separately) { return planes <= 32 && !pack_separately; }
+inline uint32_t stem_cin_pad(uint32_t planes, uint32_t row_channels, bool f16x2, bool pack_separately) {
+    const uint32_t to = f16x2 && !stem_is_fused(planes, pack_separately) ? 64 : row_channels;
+    return (planes + to - 1) / to * to;
+}
+
 inline uint16_t f32_to_bf16(float f) {
     uint32_t u;
     memcpy(&u, &f, 4);

@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "cattus_hip_tower_kernel",
     "cattus_hip_create_diag",  # include/cattus_hip_diag.h
     "cattus_hip_stream_shift",  # include/cattus_hip_diag.h
+    "cattus_hip_stem_input",  # include/cattus_hip_diag.h
 ]
 
 
@@ -144,6 +145,7 @@ def load_library():
     L.cattus_hip_tower_kernel.argtypes = [vp]
     L.cattus_hip_tower_kernel.restype = C.c_char_p
     L.cattus_hip_stream_shift.argtypes = [vp]
+    L.cattus_hip_stem_input.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("cattus_hip_last_error", "cattus_hip_version", "cattus_hip_runtime_note", "cattus_hip_host_alloc",
@@ -322,6 +324,14 @@ class HipEvaluator:
     def stream_shift(self) -> int:
         """t: the f16 towers carry the residual stream at 2^t times its size (0 for f32 and bf16; include/cattus_hip_diag.h)."""
         return self._lib.cattus_hip_stream_shift(self._h)
+
+    def stem_input(self) -> tuple[int, bool]:
+        """(input channels of the stem conv as laid out on the device, whether the plane pack runs as its own launch in front of it):
+        include/cattus_hip_diag.h.  f16x2 has 32 channels where the stem expands the planes itself, a multiple of 64 where they are
+        packed first (more than 32 planes, or CATTUS_FUSED_STEM=0)."""
+        channels, packed = C.c_uint32(), C.c_uint32()
+        _check(self._lib.cattus_hip_stem_input(self._h, C.byref(channels), C.byref(packed)))
+        return channels.value, bool(packed.value)
 
     def mfma_sustained(self, seconds: float = 1.0) -> float:
         """TFLOP/s the device's matrix pipe sustains on back-to-back MFMAs of this evaluator's tower kind (diagnostic)."""

@@ -50,6 +50,8 @@ typedef enum cattus_dtype {
      * significand bits; outside the reference's cross-runtime tolerance (DESIGN.md section 4 for what it does to a search). */
     CATTUS_DTYPE_F16 = 3,
 } cattus_dtype;
+/* Every dtype takes any network the blob format and the plane pack allow: up to 128 plane words per leaf (planes x plane_words),
+ * e.g. AlphaZero's 119 chess planes. */
 
 /* Form of the f16x2 conv tower on 8x8 boards with a multiple of 128 filters.  The two forms agree to < 2e-6 per logit but not
  * bit for bit, and a leaf's bits must not depend on the batch it came in: the form is fixed per evaluator, here. */
@@ -94,7 +96,9 @@ typedef struct cattus_net_desc {
  * `cfg`; the library reads two operational environment variables and no other: CATTUS_HIP_WAIT=block (the host thread sleeps
  * on an event instead of spinning while a batch runs) and CATTUS_ROCTX=1 (ROCTx ranges around every batch).  The A/B switches
  * of the tests and timing scripts go through cattus_hip_create_diag (cattus_hip_diag.h), never through the environment; the
- * same header declares cattus_hip_stream_shift(), what an f16 / f16x2 evaluator chose for its residual stream. */
+ * same header declares cattus_hip_stream_shift(), what an f16 / f16x2 evaluator chose for its residual stream, and
+ * cattus_hip_stem_input(), how the stem gets its input.  A network of more than 128 plane words per
+ * leaf (planes x cfg->plane_words) is refused with CATTUS_E_UNSUPPORTED, whatever the dtype; up to there every dtype takes it. */
 int cattus_hip_create(const void* weights, size_t nbytes, const cattus_eval_config* cfg, cattus_eval** out);
 void cattus_hip_destroy(cattus_eval* e);
 int cattus_hip_desc(const cattus_eval* e, cattus_net_desc* out);

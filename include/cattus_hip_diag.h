@@ -19,7 +19,8 @@ extern "C" {
  *   CATTUS_T64_CH=2|4, CATTUS_T64_LS=0, CATTUS_T64S_SHAPE=1|2, CATTUS_T64S_HEADS=0   workgroup shapes of the resident towers
  *   CATTUS_SPLIT_W=0        f16x2 direct form: weights through the LDS ring (conv3x3_split_kernel) instead of the register ring
  *   CATTUS_CONV_CB=1|2, CATTUS_CONV_PBW=1|2   tile shapes of the per-layer conv kernels
- *   CATTUS_FUSED_STEM=0     plane pack as its own launch in front of the stem
+ *   CATTUS_FUSED_STEM=0     every dtype: the plane pack as its own launch in front of the stem, which then runs as an ordinary layer (what
+ *                           a network of more than 32 planes runs anyway; f16x2: stem input channels padded to 64 instead of 32)
  *   CATTUS_FORCE_GENERIC=1  the one-thread-per-output f32 path (a second checker of the MFMA kernels)
  *   CATTUS_WINO_KERNEL=k16|k4   Winograd form: the 16-frequencies-per-wave kernel (conv3x3_wino_kernel) or the 4-frequencies x
  *                               2x2-blocks one (conv3x3_wino4_kernel / tower_wino4_kernel); same bits (an eight-wave kernel, two waves
@@ -37,6 +38,13 @@ int cattus_hip_create_diag(const void* weights, size_t nbytes, const cattus_eval
  * power-of-two weight products, chosen once from the network at create time; evaluator.hip, choose_stream_shift).  0 for f32
  * and bf16, for a network whose stream is not small, and under CATTUS_STREAM_SHIFT=0. */
 int cattus_hip_stream_shift(const cattus_eval* e);
+
+/* How the stem conv gets its input.  *channels: its input channels as laid out on the device (the planes padded with zero channels;
+ * weight_layout.h, stem_cin_pad): f16x2 32 where the stem expands the planes itself and a multiple of 64 where they are packed first,
+ * bf16 / f16 a multiple of 64, f32 a multiple of 32; the plane count itself on the towers that pad nothing.  *packed: 1 where the
+ * plane pack runs as its own launch in front of the stem (per-layer and Winograd towers of a network of more than 32 planes, or under
+ * CATTUS_FUSED_STEM=0), 0 where the stem kernel or a one-launch tower expands the planes itself.  Either pointer may be NULL. */
+int cattus_hip_stem_input(const cattus_eval* e, uint32_t* channels, uint32_t* packed);
 
 #ifdef __cplusplus
 }
