@@ -102,7 +102,14 @@ Folded fold_conv(const float* w, uint32_t cout, uint32_t cin, uint32_t taps, con
 // stream's RMS.  S >= 1/2 keeps t = 0: the weights, and so the bits, of a tower without the shift (every seeded network: S lies in
 // [0.9, 2.7), near 1 where the blocks are few).  A smaller S is lifted into [1, 2): t = -floor(log2 S), at most 16; 0 where S is 0
 // or not finite.
-int choose_stream_shift(const cattus_net_desc& d, const float* p) {
+// One t for the tower leaves the cliff in place channel by channel: a trained network's channels differ in scale, and a channel that
+// runs below 2^-3 beside a median of O(1) still stores subnormal lo halves.  The products above are per channel anyway -- channel k is
+// an output row of the stem and of every conv2 and an input column of every conv1 and of the head convs -- so channel k is carried at
+// 2^t_k, t_k = t + r_k: with s_k the same estimate for channel k alone, r_k = 0 where s_k 2^t >= 1/2 (every seeded channel: s_k >= 0.75,
+// the same bits again) and where s_k is 0 (a dead channel) or not finite; a smaller channel is lifted into [1, 2) as S is, t_k at most
+// 16.  The rule itself is weight_layout.h's stream_shifts (tests/weight_layout_check.cpp); t is what cattus_hip_stream_shift reports,
+// every t_k what cattus_hip_stream_shifts does.
+std::vector<int> choose_stream_shift(const cattus_net_desc& d, const float* p, int* t) {
     const uint32_t F = d.filters;
     const float* g0 = p + (size_t)F * d.planes * 9;
     const float* b0 = g0 + F;
@@ -114,16 +121,16 @@ int choose_stream_shift(const cattus_net_desc& d, const float* p) {
         const float* b2 = g2 + F;
         for (uint32_t c = 0; c < F; c++) s[c] += (double)g2[c] * g2[c] + (double)b2[c] * b2[c];
     }
-    std::sort(s.begin(), s.end());
-    const double S = std::sqrt(F % 2 ? s[F / 2] : 0.5 * (s[F / 2 - 1] + s[F / 2]));
-    if (!(S > 0.0) || !std::isfinite(S) || S >= 0.5) return 0;
-    return std::min(16, -ilogb(S));
+    *t = stream_shift_global(s);
+    return stream_shifts(s);
 }
 
-// w x 2^sw, b x 2^sb (exact: powers of two)
-void shift_folded(Folded& f, int sw, int sb) {
-    for (float& x : f.w) x = ldexpf(x, sw);
-    for (float& x : f.b) x = ldexpf(x, sb);
+// A folded layer whose output channels write the stream, or whose input channels read it, with stream channel k at 2^tk[k] times
+// its size (exact: powers of two): writes, output channel k's w, b x 2^tk[k]; reads, input channel k's w x 2^-tk[k]
+void shift_folded(Folded& f, uint32_t cin, const std::vector<int>& tk, bool writes) {
+    const size_t cout = f.b.size();  // w [taps][cout][cin]
+    for (size_t i = 0; i < f.w.size(); i++) f.w[i] = ldexpf(f.w[i], writes ? tk[i / cin % cout] : -tk[i % cin]);
+    for (size_t co = 0; writes && co < cout; co++) f.b[co] = ldexpf(f.b[co], tk[co]);
 }
 
 // One device allocation that a tower's hot buffers are carved from (the Winograd tower: the transformed weights of all layers and
@@ -322,9 +329,11 @@ struct cattus_eval {
     // wait) -- that batch is run again on the per-layer launches, and so is every later one
     std::atomic<bool> tower_gave_up{false};
     uint32_t persist_spin = 1u << 18, cus = 0;
-    // the f16 towers carry the residual stream at 2^stream_shift times its size (choose_stream_shift); CATTUS_STREAM_SHIFT=0: never
+    // the f16 towers carry the residual stream at 2^stream_shift times its size, channel k of it at 2^stream_shifts[k] >= that
+    // (choose_stream_shift); CATTUS_STREAM_SHIFT=0: never
     bool stream_shift_on = true;
     int stream_shift = 0;
+    std::vector<int> stream_shifts;
     // tile-forcing switches (CATTUS_CONV_CB, CATTUS_CONV_PBW: A/B runs, the tile-equality tests) and the f16 towers' saturation
     // counter: this evaluator's own -- a second evaluator in the process (model1 vs model2) neither re-tiles nor shares them
     ConvOpts conv_opts;
@@ -467,12 +476,15 @@ int build(cattus_eval* e, const float* p) {
     const uint32_t F = d.filters, hw = e->hw, FP = e->fpad;
     auto take = [&](size_t n) { return (p += n) - n; };  // the next n floats of the blob
     int rc;
-    const int t = e->stream_shift = act_f16_family(e->act) && e->stream_shift_on ? choose_stream_shift(d, p) : 0;
+    e->stream_shifts.assign(F, 0);
+    if (act_f16_family(e->act) && e->stream_shift_on) e->stream_shifts = choose_stream_shift(d, p, &e->stream_shift);
+    const std::vector<int>& tk = e->stream_shifts;
+    const bool shifted = std::any_of(tk.begin(), tk.end(), [](int t) { return t != 0; });
     {
         const float* w = take((size_t)F * d.planes * 9);
         const float *g = take(F), *be = take(F), *mu = take(F), *var = take(F);
         Folded f = fold_conv(w, F, d.planes, 9, g, be, mu, var);
-        if (t) shift_folded(f, t, t);
+        if (shifted) shift_folded(f, d.planes, tk, true);
         if ((rc = upload_conv(e, e->stem, f, F, d.planes, true))) return rc;
     }
     for (uint32_t i = 0; i < d.blocks; i++) {
@@ -481,12 +493,12 @@ int build(cattus_eval* e, const float* p) {
         const float* w1 = take((size_t)F * F * 9);
         const float *mu1 = take(F), *var1 = take(F);
         Folded f1 = fold_conv(w1, F, F, 9, nullptr, nullptr, mu1, var1);
-        if (t) shift_folded(f1, -t, 0);
+        if (shifted) shift_folded(f1, F, tk, false);
         if ((rc = upload_conv(e, *e->c1.back(), f1, F, F))) return rc;
         const float* w2 = take((size_t)F * F * 9);
         const float *g2 = take(F), *be2 = take(F), *mu2 = take(F), *var2 = take(F);
         Folded f2 = fold_conv(w2, F, F, 9, g2, be2, mu2, var2);
-        if (t) shift_folded(f2, t, t);
+        if (shifted) shift_folded(f2, F, tk, true);
         if ((rc = upload_conv(e, *e->c2.back(), f2, F, F))) return rc;
     }
     // heads: value rows first, then policy rows, in one [vhc+phc][F] 1x1 conv
@@ -503,7 +515,7 @@ int build(cattus_eval* e, const float* p) {
     Folded fp = fold_conv(pw, d.phc, F, 1, nullptr, nullptr, pmu, pvar);
     const float* pfc_w = take((size_t)d.moves * d.phc * hw);
     const float* pfc_b = take(d.moves);
-    if (t) shift_folded(fv, -t, 0), shift_folded(fp, -t, 0);  // f32 rows on every path that runs an f16 tower (head_act)
+    if (shifted) shift_folded(fv, F, tk, false), shift_folded(fp, F, tk, false);  // f32 rows on every path that runs an f16 tower (head_act)
     memcpy(hw_w.data(), fv.w.data(), fv.w.size() * 4);
     memcpy(hw_w.data() + fv.w.size(), fp.w.data(), fp.w.size() * 4);
     memcpy(hw_b.data(), fv.b.data(), fv.b.size() * 4);
@@ -968,6 +980,13 @@ CATTUS_API const char* cattus_hip_tower_kernel(const cattus_eval* e) {
 }
 
 CATTUS_API int cattus_hip_stream_shift(const cattus_eval* e) { return e ? e->stream_shift : 0; }
+
+CATTUS_API int cattus_hip_stream_shifts(const cattus_eval* e, int* out, uint32_t n) {
+    if (!e || (n && !out)) return fail(CATTUS_E_INVALID, "NULL argument");
+    if (n != e->stream_shifts.size()) return fail(CATTUS_E_INVALID, "stream_shifts: %u entries asked for, the tower has %zu channels", n, e->stream_shifts.size());
+    std::copy(e->stream_shifts.begin(), e->stream_shifts.end(), out);
+    return CATTUS_OK;
+}
 
 CATTUS_API int cattus_hip_stem_input(const cattus_eval* e, uint32_t* channels, uint32_t* packed) {
     if (!e) return fail(CATTUS_E_INVALID, "NULL argument");

@@ -44,6 +44,33 @@ inline uint16_t f32_to_bf16(float f) {
 // in the epilogue -- undoes the scale exactly.
 inline int channel_shift(double max_abs) { return max_abs > 0.0 && std::isfinite(max_abs) ? std::min(100, std::max(-100, 10 - ilogb(max_abs))) : 0; }
 
+// The f16 towers' stream shifts (evaluator.hip, choose_stream_shift, has the why).  s2[k] = sum of gamma^2 + beta^2 of stream channel k over
+// the BatchNorms that write the stream, so sqrt(s2[k]) = s_k estimates the channel's RMS.  stream_shift_global: S = sqrt(median s2); 0 for
+// S >= 1/2 (and for S = 0 or not finite), else -floor(log2 S), at most STREAM_SHIFT_MAX.
+constexpr int STREAM_SHIFT_MAX = 16;
+inline int stream_shift_global(std::vector<double> s2) {
+    const size_t n = s2.size();
+    if (!n) return 0;
+    std::sort(s2.begin(), s2.end());
+    const double S = std::sqrt(n % 2 ? s2[n / 2] : 0.5 * (s2[n / 2 - 1] + s2[n / 2]));
+    if (!(S > 0.0) || !std::isfinite(S) || S >= 0.5) return 0;
+    return std::min(STREAM_SHIFT_MAX, -ilogb(S));
+}
+// Channel k's own shift t_k = t + r_k >= t, t the global one: r_k = 0 where s_k 2^t >= 1/2 and where s_k is 0 (a dead channel) or not
+// finite; a smaller channel is lifted into [1, 2), r_k = -floor(log2(s_k 2^t)), with t_k at most STREAM_SHIFT_MAX -- a bound on every
+// exponent that the f32 products w 2^-t_k and the per-channel weight scales (channel_shift: within +-100) have to absorb.
+inline int stream_shift_channel(double s2_k, int t) {
+    const double s = std::sqrt(s2_k);
+    if (!(s > 0.0) || !std::isfinite(s) || ldexp(s, t) >= 0.5) return t;
+    return std::min(STREAM_SHIFT_MAX, -ilogb(s));  // = t - floor(log2(s 2^t)) > t
+}
+inline std::vector<int> stream_shifts(const std::vector<double>& s2) {
+    const int t = stream_shift_global(s2);
+    std::vector<int> tk(s2.size());
+    for (size_t k = 0; k < s2.size(); k++) tk[k] = stream_shift_channel(s2[k], t);
+    return tk;
+}
+
 // [cout_pad biases | cout_pad inverse scales 2^-shift]; without shifts (f32, bf16) the biases alone
 inline std::vector<float> bias_and_scales(const Folded& f, const ConvShape& s, const std::vector<int>* shift = nullptr) {
     std::vector<float> b((size_t)(shift ? 2 : 1) * s.cout_pad, 0.0f);

@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "cattus_hip_tower_kernel",
     "cattus_hip_create_diag",  # include/cattus_hip_diag.h
     "cattus_hip_stream_shift",  # include/cattus_hip_diag.h
+    "cattus_hip_stream_shifts",  # include/cattus_hip_diag.h
     "cattus_hip_stem_input",  # include/cattus_hip_diag.h
 ]
 
@@ -145,6 +146,7 @@ def load_library():
     L.cattus_hip_tower_kernel.argtypes = [vp]
     L.cattus_hip_tower_kernel.restype = C.c_char_p
     L.cattus_hip_stream_shift.argtypes = [vp]
+    L.cattus_hip_stream_shifts.argtypes = [vp, C.POINTER(C.c_int), C.c_uint32]
     L.cattus_hip_stem_input.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
@@ -324,6 +326,12 @@ class HipEvaluator:
     def stream_shift(self) -> int:
         """t: the f16 towers carry the residual stream at 2^t times its size (0 for f32 and bf16; include/cattus_hip_diag.h)."""
         return self._lib.cattus_hip_stream_shift(self._h)
+
+    def stream_shifts(self) -> np.ndarray:
+        """t_k per stream channel (filters entries, each >= stream_shift(); include/cattus_hip_diag.h)."""
+        out = np.zeros(self.desc.filters, dtype=np.intc)
+        _check(self._lib.cattus_hip_stream_shifts(self._h, out.ctypes.data_as(C.POINTER(C.c_int)), len(out)))
+        return out
 
     def stem_input(self) -> tuple[int, bool]:
         """(input channels of the stem conv as laid out on the device, whether the plane pack runs as its own launch in front of it):

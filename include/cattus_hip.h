@@ -96,8 +96,8 @@ typedef struct cattus_net_desc {
  * `cfg`; the library reads two operational environment variables and no other: CATTUS_HIP_WAIT=block (the host thread sleeps
  * on an event instead of spinning while a batch runs) and CATTUS_ROCTX=1 (ROCTx ranges around every batch).  The A/B switches
  * of the tests and timing scripts go through cattus_hip_create_diag (cattus_hip_diag.h), never through the environment; the
- * same header declares cattus_hip_stream_shift(), what an f16 / f16x2 evaluator chose for its residual stream, and
- * cattus_hip_stem_input(), how the stem gets its input.  A network of more than 128 plane words per
+ * same header declares cattus_hip_stream_shift() and cattus_hip_stream_shifts(), what an f16 / f16x2 evaluator chose for its
+ * residual stream and for each channel of it, and cattus_hip_stem_input(), how the stem gets its input.  A network of more than 128 plane words per
  * leaf (planes x cfg->plane_words) is refused with CATTUS_E_UNSUPPORTED, whatever the dtype; up to there every dtype takes it. */
 int cattus_hip_create(const void* weights, size_t nbytes, const cattus_eval_config* cfg, cattus_eval** out);
 void cattus_hip_destroy(cattus_eval* e);

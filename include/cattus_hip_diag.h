@@ -39,6 +39,11 @@ int cattus_hip_create_diag(const void* weights, size_t nbytes, const cattus_eval
  * and bf16, for a network whose stream is not small, and under CATTUS_STREAM_SHIFT=0. */
 int cattus_hip_stream_shift(const cattus_eval* e);
 
+/* The same per channel: out[k] = t_k >= t, n = the network's filters (anything else: CATTUS_E_INVALID).  Channel k of the stream is
+ * carried at 2^t_k times its size; t_k > t where channel k alone is small beside the median one (weight_layout.h, stream_shifts).
+ * All 0 wherever cattus_hip_stream_shift is 0 by dtype or switch. */
+int cattus_hip_stream_shifts(const cattus_eval* e, int* out, uint32_t n);
+
 /* How the stem conv gets its input.  *channels: its input channels as laid out on the device (the planes padded with zero channels;
  * weight_layout.h, stem_cin_pad): f16x2 32 where the stem expands the planes itself and a multiple of 64 where they are packed first,
  * bf16 / f16 a multiple of 64, f32 a multiple of 32; the plane count itself on the towers that pad nothing.  *packed: 1 where the

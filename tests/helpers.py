@@ -114,3 +114,65 @@ def stream_twin(desc: NetDesc, tensors: dict, c: float) -> dict:
         out[p + "running_mean"] = (f64(p + "running_mean") * c).astype(np.float32)
         out[p + "running_var"] = var.astype(np.float32)
     return out
+
+
+F32_MIN_NORMAL, F32_MAX = 2.0**-126, float(np.finfo(np.float32).max)
+
+
+def channel_twin(desc: NetDesc, tensors: dict, exponents) -> dict:
+    """The tensors of a network that computes the same function as ``tensors`` with channel k of its residual stream multiplied
+    by c_k = 2^exponents[k] (integers, one per filter): gamma, beta of the stem BatchNorm and of every block's _bn2 x c_k; the
+    weights that read channel k -- input channel k of every block's _conv1 and of both head convs -- / c_k.  (ReLU commutes with
+    c_k > 0, the skip adds channel k to channel k, and _bn1 and the head BatchNorms normalise what the convs write, which does not
+    move.)  Every product is by a power of two and so exact: unlike stream_twin's, this twin's float64 run equals the base
+    network's to the bit, and so do the f32 outputs of anything that folds and sums in the oracle's order.  Computed in float64,
+    returned as float32; a wrong number of exponents, or a product that leaves the f32 normal range (and would round), raises."""
+    e = np.asarray(exponents)
+    if e.shape != (desc.filters,) or not np.issubdtype(e.dtype, np.integer):
+        raise ValueError(f"channel_twin: want {desc.filters} integer exponents, got {e.dtype} {e.shape}")
+    c = np.ldexp(1.0, e.astype(np.int64))
+    out = dict(tensors)
+
+    def scaled(k, factor):
+        x = np.asarray(tensors[k], dtype=np.float64) * factor
+        a = np.abs(x[x != 0])
+        if a.size and not (a.min() >= F32_MIN_NORMAL and a.max() <= F32_MAX):
+            raise ValueError(f"channel_twin: {k} leaves the f32 normal range")
+        out[k] = x.astype(np.float32)
+
+    for p in ["_conv1._bn."] + [f"_residual_blocks.{i}._bn2." for i in range(desc.blocks)]:
+        scaled(p + "weight", c)
+        scaled(p + "bias", c)
+    readers = [f"_residual_blocks.{i}._conv1.weight" for i in range(desc.blocks)] + ["_value_head.0._conv.weight", "_policy_head.0._conv.weight"]
+    for k in readers:
+        scaled(k, (1.0 / c).reshape(1, -1, 1, 1))
+    return out
+
+
+def hostile_tensors(desc: NetDesc, tensors: dict) -> dict:
+    """A *different* network, of statistics that seeded_tensors never draws, to be compared with its own forward_f64: on the stem
+    BatchNorm and every block's _bn2, gamma's sign flipped where k % 3 == 1 and gamma = beta = 0 where k % 16 == 5 (dead stream
+    channels, unless a later _bn2 revives them -- none does: all are zeroed alike); in every block's _conv1, the weights of output
+    channels k % 16 == 9 zeroed (an all-zero folded row: the middle activation of that channel is relu of its bias alone)."""
+    out = dict(tensors)
+    k = np.arange(desc.filters)
+    for p in ["_conv1._bn."] + [f"_residual_blocks.{i}._bn2." for i in range(desc.blocks)]:
+        g, b = np.array(tensors[p + "weight"], dtype=np.float32), np.array(tensors[p + "bias"], dtype=np.float32)
+        g[k % 3 == 1] *= -1
+        g[k % 16 == 5] = 0
+        b[k % 16 == 5] = 0
+        out[p + "weight"], out[p + "bias"] = g, b
+    for i in range(desc.blocks):
+        w = np.array(tensors[f"_residual_blocks.{i}._conv1.weight"], dtype=np.float32)
+        w[k % 16 == 9] = 0
+        out[f"_residual_blocks.{i}._conv1.weight"] = w
+    return out
+
+
+# channel_twin exponents by filter count F: channels of a stream that differ in scale by 2^8 or more
+CHANNEL_PATTERNS = {
+    "Q8": lambda F: np.where(np.arange(F) % 4 == 1, -8, 0),  # every fourth channel small beside a unit median
+    "W8": lambda F: np.random.default_rng(3).integers(-8, 9, F),  # every scale from 2^-8 to 2^8
+    "M8": lambda F: np.where(np.arange(F) % 4 == 1, 0, -8),  # a small median, every fourth channel 2^8 above it
+    "S8": lambda F: (7 * np.arange(F)) % 17 - 8,  # an even spread over 2^-8 .. 2^8
+}

@@ -95,7 +95,41 @@ static void check_wino(uint32_t n, uint32_t pad) {
     for (uint32_t co = n; co < pad; co++) CHECK(sh[co] == 0, "U scale of padded channel %u", co);
 }
 
+// the stream-shift rule on per-channel sums of gamma^2 + beta^2 (s2; s = sqrt(s2) is what the rule speaks of)
+static void check_stream_shifts() {
+    auto sq = [](double s) { return s * s; };
+    // the global part: the median, 0 from 1/2 up, lifted into [1, 2) below, at most 16, 0 for nothing to go by
+    CHECK(stream_shift_global({}) == 0 && stream_shift_global({sq(0.5)}) == 0 && stream_shift_global({sq(0.49)}) == 2, "global shift at 1/2");
+    CHECK(stream_shift_global({sq(0.25), 1.0, sq(0.01)}) == 2 && stream_shift_global({1.0, sq(0.25), 1.0, sq(0.25)}) == 0, "global shift is the median's");
+    CHECK(stream_shift_global({sq(ldexp(1.5, -8))}) == 8 && stream_shift_global({sq(ldexp(1.0, -30))}) == 16, "global shift size and cap");
+    CHECK(stream_shift_global({0.0, 0.0, 1.0}) == 0 && stream_shift_global({INFINITY}) == 0 && stream_shift_global({NAN}) == 0, "global shift of 0 / inf / nan");
+    // a channel: t where s 2^t >= 1/2, where s is 0 or not finite; else lifted into [1, 2), at most 16
+    CHECK(stream_shift_channel(sq(0.75), 0) == 0 && stream_shift_channel(sq(0.5), 0) == 0 && stream_shift_channel(sq(300.0), 0) == 0, "channels that stay");
+    CHECK(stream_shift_channel(0.0, 0) == 0 && stream_shift_channel(0.0, 5) == 5 && stream_shift_channel(INFINITY, 3) == 3 && stream_shift_channel(NAN, 3) == 3, "dead and non-finite channels");
+    CHECK(stream_shift_channel(sq(0.49), 0) == 2 && stream_shift_channel(sq(0.25), 0) == 2 && stream_shift_channel(sq(0.2), 0) == 3, "channels just below 1/2");
+    CHECK(stream_shift_channel(sq(ldexp(1.0, -8)), 0) == 8 && stream_shift_channel(sq(ldexp(1.99, -8)), 0) == 8 && stream_shift_channel(sq(ldexp(0.99, -8)), 0) == 9, "a channel at 2^-8");
+    CHECK(stream_shift_channel(sq(ldexp(1.0, -8)), 8) == 8 && stream_shift_channel(sq(ldexp(1.0, -9)), 8) == 8 && stream_shift_channel(sq(ldexp(1.0, -10)), 8) == 10, "remainder on a shifted tower");
+    CHECK(stream_shift_channel(sq(1.0), 8) == 8 && stream_shift_channel(sq(ldexp(1.0, -40)), 0) == 16 && stream_shift_channel(sq(ldexp(1.0, -40)), 16) == 16, "large channels; the cap");
+    CHECK(stream_shift_channel(sq(ldexp(1.0, -600)), 0) == 0, "s2 underflows to 0: dead");
+    for (int t = 0; t <= 16; t++)
+        for (int e = -45; e <= 10; e++)
+            for (double m : {1.0, 1.25, 1.999}) {
+                const double s = ldexp(m, e);
+                const int tk = stream_shift_channel(sq(s), t);
+                CHECK(tk >= t && tk <= STREAM_SHIFT_MAX, "t_k %d outside [t, 16] (s %g, t %d)", tk, s, t);
+                if (ldexp(s, t) >= 0.5) CHECK(tk == t, "s 2^t >= 1/2 moved (s %g, t %d)", s, t);
+                else if (tk < STREAM_SHIFT_MAX) CHECK(ldexp(s, tk) >= 1.0 && ldexp(s, tk) < 2.0, "s 2^t_k = %g not in [1, 2) (s %g, t %d)", ldexp(s, tk), s, t);
+            }
+    // all of it: Q8-like (every fourth channel at 2^-8 beside unit ones), a dead channel, and the reverse (unit channels beside a small median)
+    const std::vector<int> q = stream_shifts({1.0, sq(ldexp(1.5, -8)), 0.0, sq(2.0), sq(ldexp(1.0, -3)), 1.0});
+    CHECK((q == std::vector<int>{0, 8, 0, 0, 3, 0}), "per-channel shifts beside a unit median");
+    const std::vector<int> m = stream_shifts({sq(ldexp(1.5, -8)), 1.0, sq(ldexp(1.5, -8)), 0.0, sq(ldexp(1.5, -12)), sq(ldexp(1.5, -8)), sq(ldexp(1.5, -8))});
+    CHECK((m == std::vector<int>{8, 8, 8, 8, 12, 8, 8}), "per-channel shifts beside a small median");
+    CHECK(stream_shifts({}).empty(), "no channels");
+}
+
 int main() {
+    check_stream_shifts();
     CHECK(channel_shift(0.0) == 0 && channel_shift(1.0) == 10 && channel_shift(1500.0) == 0 && channel_shift(2048.0) == -1 && channel_shift(INFINITY) == 0, "channel_shift");
     check_direct(3, 5, 64, 32);   // one 32-channel chunk
     check_direct(3, 70, 64, 96);  // three chunks (the third partly filled), both k-halves and both 8-groups of a chunk
