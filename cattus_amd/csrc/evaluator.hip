@@ -125,6 +125,13 @@ std::vector<int> choose_stream_shift(const cattus_net_desc& d, const float* p, i
     return stream_shifts(s);
 }
 
+// What cattus_hip_create_calibrated measured on its sample positions (cattus_hip_stream_range of an f32 evaluator of the same blob): per
+// stream channel the mean square and the largest |value|.  With it build() takes weight_layout.h's calibrated_stream_shifts in place of
+// choose_stream_shift: the estimate above is exact only while every BatchNorm input has unit variance under its running statistics and
+// nothing but gamma / beta carries the scale -- a channel whose conv rows, running_mean and beta are all 2^-8 of a unit channel's beside
+// an unchanged gamma is the same function with s_k = O(1) and a stream at 2^-8.
+struct Calibration { std::vector<double> s2, abs_max; };
+
 // A folded layer whose output channels write the stream, or whose input channels read it, with stream channel k at 2^tk[k] times
 // its size (exact: powers of two): writes, output channel k's w, b x 2^tk[k]; reads, input channel k's w x 2^-tk[k]
 void shift_folded(Folded& f, uint32_t cin, const std::vector<int>& tk, bool writes) {
@@ -267,6 +274,9 @@ struct Lane {
     DevBuf d_planes, x0, a, t, y, hv, h1, d_policy, d_value;
     DevBuf d_legal_idx, d_legal_cnt, d_probs;  // legal-move softmax operands, allocated on first use
     uint32_t legal_stride = 0;
+    // cattus_hip_stream_range, allocated on first use: the range kernel's workgroup partials, and the per-channel accumulators
+    // [fpad sums of squares (double) | fpad maxima (float)] that collect over a call's tensors and chunks, ordered by `stream`
+    DevBuf range_part_sq, range_part_max, range_acc;
     PinnedBuf h_planes, h_policy, h_value;
     // the Winograd tower in one launch (tower_wino4_kernel): this lane's layer table, hand-off counters and error word, and the
     // page-locked word the error word is copied to behind every such launch
@@ -330,7 +340,8 @@ struct cattus_eval {
     std::atomic<bool> tower_gave_up{false};
     uint32_t persist_spin = 1u << 18, cus = 0;
     // the f16 towers carry the residual stream at 2^stream_shift times its size, channel k of it at 2^stream_shifts[k] >= that
-    // (choose_stream_shift); CATTUS_STREAM_SHIFT=0: never
+    // (choose_stream_shift; from cattus_hip_create_calibrated: calibrated_stream_shifts, whose headroom guard can take a channel
+    // below the global shift); CATTUS_STREAM_SHIFT=0: never
     bool stream_shift_on = true;
     int stream_shift = 0;
     std::vector<int> stream_shifts;
@@ -469,7 +480,7 @@ int build_simple(cattus_eval* e, const float* p) {
     return CATTUS_OK;
 }
 
-int build(cattus_eval* e, const float* p) {
+int build(cattus_eval* e, const float* p, const Calibration* cal) {
     const cattus_net_desc& d = e->d;
     const TowerPlan& plan = e->plan;
     if (plan.kind == TowerKind::Simple) return build_simple(e, p);
@@ -477,7 +488,10 @@ int build(cattus_eval* e, const float* p) {
     auto take = [&](size_t n) { return (p += n) - n; };  // the next n floats of the blob
     int rc;
     e->stream_shifts.assign(F, 0);
-    if (act_f16_family(e->act) && e->stream_shift_on) e->stream_shifts = choose_stream_shift(d, p, &e->stream_shift);
+    if (act_f16_family(e->act) && e->stream_shift_on) {
+        if (cal) e->stream_shifts = calibrated_stream_shifts(cal->s2, cal->abs_max), e->stream_shift = stream_shift_global(cal->s2);
+        else e->stream_shifts = choose_stream_shift(d, p, &e->stream_shift);
+    }
     const std::vector<int>& tk = e->stream_shifts;
     const bool shifted = std::any_of(tk.begin(), tk.end(), [](int t) { return t != 0; });
     {
@@ -629,6 +643,7 @@ struct Forward {
     float *d_policy, *d_value;
     hipStream_t st;
     TowerTimer* tt;
+    bool observe;  // cattus_hip_stream_range: the range kernel behind every stream tensor of per_layer(); false on every other call
     const cattus_net_desc& d = e->d;
     const uint32_t w64 = e->cfg.plane_words, S = d.board, F = d.filters, FP = e->fpad;
     float *a = L.a.as<float>(), *t = L.t.as<float>(), *y = L.y.as<float>();
@@ -706,13 +721,21 @@ struct Forward {
                             (e->plan.w_frag ? CONV_W_FRAG : 0) | flags, e->conv_opts);
     }
 
+    // the f32 tower's stream tensor in `a` (plain f32 rows) into the lane's range accumulators
+    void observe_stream() {
+        double* const acc_sq = L.range_acc.as<double>();
+        launch_stream_range(a, nb, n, S, FP, L.range_part_sq.as<double>(), L.range_part_max.as<float>(), acc_sq, reinterpret_cast<float*>(acc_sq + FP), st);
+    }
+
     const void* per_layer() {
         const int last_flags = act_f16_family(e->act) ? CONV_OUT_F32 : 0;  // the f16 towers hand the f32 head kernels plain f32 rows
         conv_mfma(e->stem, L.x0.p, nullptr, a, d.blocks == 0 ? last_flags : 0, true);
+        if (observe) observe_stream();
         for (uint32_t i = 0; i < d.blocks; i++) {
             conv_mfma(*e->c1[i], a, nullptr, t, 0);
             conv_mfma(*e->c2[i], t, a, y, i + 1 == d.blocks ? last_flags : 0);
             std::swap(a, y);
+            if (observe) observe_stream();
         }
         return a;
     }
@@ -771,9 +794,10 @@ struct Forward {
     }
 };
 
-int enqueue_forward(cattus_eval* e, Lane& L, const uint64_t* d_planes, uint32_t n, float* d_policy, float* d_value, hipStream_t st, TowerTimer* tt = nullptr) {
+int enqueue_forward(cattus_eval* e, Lane& L, const uint64_t* d_planes, uint32_t n, float* d_policy, float* d_value, hipStream_t st, TowerTimer* tt = nullptr,
+                    bool observe = false) {
     const uint32_t bpw = e->plan.tuned() ? ROWS_PER_WG / e->slots : 1;  // boards per workgroup of the conv kernel
-    Forward f{e, L, d_planes, n, (n + bpw - 1) / bpw * bpw, d_policy, d_value, st, tt};
+    Forward f{e, L, d_planes, n, (n + bpw - 1) / bpw * bpw, d_policy, d_value, st, tt, observe};
     switch (e->plan.kind) {
         case TowerKind::Simple: f.simple(); break;
         case TowerKind::Generic: f.heads_generic(f.generic()); break;
@@ -823,25 +847,26 @@ struct LegalArgs {
     float* probs;  // [n][stride]
 };
 
+// A lane for one blocking call, locked: a free one if there is one, else queue on one of them in turn.
+Lane& take_lane(cattus_eval* e, std::unique_lock<std::mutex>& lk) {
+    for (Lane& cand : e->lanes) {
+        std::unique_lock<std::mutex> tl(cand.mu, std::try_to_lock);
+        if (tl.owns_lock()) {
+            lk = std::move(tl);
+            return cand;
+        }
+    }
+    Lane& lane = e->lanes[e->lane_rr.fetch_add(1) % NLANES];
+    lk = std::unique_lock<std::mutex>(lane.mu);
+    return lane;
+}
+
 // Blocking host-buffer evaluation; caller holds no lock.  With `lg` the logits stay on the device and
 // the per-leaf softmax over the legal moves comes back instead (policy is not written).
 int eval_host(cattus_eval* e, const uint64_t* planes, uint32_t n, float* policy, float* value, const LegalArgs* lg = nullptr) {
     const cattus_net_desc& d = e->d;
-    // a free lane if there is one, else queue on one of them in turn
     std::unique_lock<std::mutex> lk;
-    Lane* lane = nullptr;
-    for (Lane& cand : e->lanes) {
-        std::unique_lock<std::mutex> tl(cand.mu, std::try_to_lock);
-        if (tl.owns_lock()) {
-            lane = &cand, lk = std::move(tl);
-            break;
-        }
-    }
-    if (!lane) {
-        lane = &e->lanes[e->lane_rr.fetch_add(1) % NLANES];
-        lk = std::unique_lock<std::mutex>(lane->mu);
-    }
-    Lane& L = *lane;
+    Lane& L = take_lane(e, lk);
     const RoctxRange range(lg ? "cattus_hip_eval_legal" : "cattus_hip_eval", n);
     HIP_TRY(hipSetDevice(e->device));
     const auto t0 = std::chrono::steady_clock::now();
@@ -1066,7 +1091,7 @@ int resolve_plan(const cattus_net_desc& d, const cattus_eval_config& cfg, const 
     return CATTUS_OK;
 }
 
-int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cfg_in, const char* switches, cattus_eval** out) {
+int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cfg_in, const char* switches, cattus_eval** out, const Calibration* cal = nullptr) {
     if (!out) return fail(CATTUS_E_INVALID, "out is NULL");
     *out = nullptr;
     if (!weights || !cfg_in) return fail(CATTUS_E_INVALID, "weights/cfg is NULL");
@@ -1175,7 +1200,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
         if (hipMalloc(&base, want) == hipSuccess) e->arena.base = (char*)base, e->arena.cap = want;
         else (void)hipGetLastError();  // no room for one block: separate allocations, as before
     }
-    if (int rc = build(e.get(), reinterpret_cast<const float*>((const char*)weights + HEADER_BYTES))) return rc;
+    if (int rc = build(e.get(), reinterpret_cast<const float*>((const char*)weights + HEADER_BYTES), cal)) return rc;
     HIP_TRY(hipDeviceSynchronize());
     {
         std::lock_guard<std::mutex> lk(e->srv_mu);
@@ -1197,6 +1222,81 @@ CATTUS_API int cattus_hip_create_diag(const void* weights, size_t nbytes, const 
 }
 
 CATTUS_API void cattus_hip_destroy(cattus_eval* e) { delete e; }
+
+CATTUS_API int cattus_hip_stream_range(cattus_eval* e, const uint64_t* planes, uint32_t n, cattus_channel_range* out, uint32_t channels) {
+    if (!e || !planes || !out) return fail(CATTUS_E_INVALID, "NULL argument");
+    if (e->act != Act::F32 || e->plan.kind != TowerKind::PerLayer)
+        return fail(CATTUS_E_UNSUPPORTED, "stream_range measures on the exact f32 tower: a dtype f32 evaluator on the MFMA per-layer tower");
+    const cattus_net_desc& d = e->d;
+    if (channels != d.filters) return fail(CATTUS_E_INVALID, "stream_range: %u entries asked for, the tower has %u channels", channels, d.filters);
+    if (n < 1) return fail(CATTUS_E_INVALID, "stream_range needs at least one leaf");
+    std::unique_lock<std::mutex> lk;
+    Lane& L = take_lane(e, lk);
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t FP = e->fpad, acc_bytes = FP * (sizeof(double) + sizeof(float));
+    if (!L.range_acc.p) {
+        const size_t parts = stream_range_parts(e->bpad, d.board);
+        int rc;
+        if ((rc = L.range_part_sq.alloc(parts * FP * sizeof(double))) || (rc = L.range_part_max.alloc(parts * FP * sizeof(float))) || (rc = L.range_acc.alloc(acc_bytes)))
+            return rc;
+    }
+    HIP_TRY(hipMemsetAsync(L.range_acc.p, 0, acc_bytes, L.stream));
+    const size_t leaf_words = (size_t)d.planes * e->cfg.plane_words;
+    for (uint32_t at = 0; at < n; at += e->cfg.max_batch) {  // the staging buffer is free again once the chunk is through
+        const uint32_t m = std::min(n - at, e->cfg.max_batch);
+        memcpy(L.h_planes.p, planes + at * leaf_words, m * leaf_words * 8);
+        HIP_TRY(hipMemcpyAsync(L.d_planes.p, L.h_planes.p, m * leaf_words * 8, hipMemcpyHostToDevice, L.stream));
+        if (int rc = enqueue_forward(e, L, L.d_planes.as<uint64_t>(), m, L.d_policy.as<float>(), L.d_value.as<float>(), L.stream, nullptr, true)) return rc;
+        HIP_TRY(hipStreamSynchronize(L.stream));
+    }
+    std::vector<double> sq(FP);
+    std::vector<float> mx(FP);
+    HIP_TRY(hipMemcpy(sq.data(), L.range_acc.p, FP * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mx.data(), (const char*)L.range_acc.p + FP * sizeof(double), FP * sizeof(float), hipMemcpyDeviceToHost));
+    const double count = (double)n * e->hw * (1 + d.blocks);  // values per channel: leaves x pixels x stream tensors
+    for (uint32_t k = 0; k < channels; k++) out[k] = cattus_channel_range{(float)std::sqrt(sq[k] / count), mx[k]};
+    return CATTUS_OK;
+}
+
+namespace {
+
+int create_calibrated_impl(const void* weights, size_t nbytes, const cattus_eval_config* cfg, const char* switches, const uint64_t* planes, uint32_t n,
+                           cattus_eval** out) {
+    if (!out) return fail(CATTUS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!weights || !cfg || !planes) return fail(CATTUS_E_INVALID, "weights/cfg/planes is NULL");
+    if (n < 1) return fail(CATTUS_E_INVALID, "calibration needs at least one leaf");
+    if (cfg->struct_size != offsetof(cattus_eval_config, tower_form) && cfg->struct_size != sizeof(cattus_eval_config))
+        return fail(CATTUS_E_INVALID, "cfg.struct_size mismatch");
+    uint32_t filters = 0;  // 0: SimpleTwoHeadedModel (or no blob at all, which create_impl refuses)
+    if (nbytes >= HEADER_BYTES) memcpy(&filters, (const char*)weights + 8 + 5 * 4, 4);
+    // only the f16 towers shift their stream: everything else is cattus_hip_create
+    if ((cfg->dtype != CATTUS_DTYPE_F16X2 && cfg->dtype != CATTUS_DTYPE_F16) || filters == 0) return create_impl(weights, nbytes, cfg, switches, out);
+    cattus_eval_config mcfg{};
+    mcfg.struct_size = sizeof mcfg, mcfg.device = cfg->device, mcfg.max_batch = std::min(n, 256u), mcfg.plane_words = cfg->plane_words;
+    mcfg.dtype = CATTUS_DTYPE_F32, mcfg.flush_us = cfg->flush_us, mcfg.tower_form = CATTUS_TOWER_AUTO;
+    cattus_eval* measure = nullptr;
+    if (int rc = create_impl(weights, nbytes, &mcfg, nullptr, &measure)) return rc;
+    std::vector<cattus_channel_range> range(filters);
+    const int rrc = cattus_hip_stream_range(measure, planes, n, range.data(), filters);
+    cattus_hip_destroy(measure);
+    if (rrc) return rrc;
+    Calibration cal;
+    for (const cattus_channel_range& r : range) cal.s2.push_back((double)r.rms * r.rms), cal.abs_max.push_back(r.abs_max);
+    return create_impl(weights, nbytes, cfg, switches, out, &cal);
+}
+
+}  // namespace
+
+CATTUS_API int cattus_hip_create_calibrated(const void* weights, size_t nbytes, const cattus_eval_config* cfg, const uint64_t* planes, uint32_t n,
+                                            cattus_eval** out) {
+    return create_calibrated_impl(weights, nbytes, cfg, nullptr, planes, n, out);
+}
+
+CATTUS_API int cattus_hip_create_calibrated_diag(const void* weights, size_t nbytes, const cattus_eval_config* cfg, const char* switches,
+                                                 const uint64_t* planes, uint32_t n, cattus_eval** out) {
+    return create_calibrated_impl(weights, nbytes, cfg, switches, planes, n, out);
+}
 
 CATTUS_API int cattus_hip_desc(const cattus_eval* e, cattus_net_desc* out) {
     if (!e || !out) return fail(CATTUS_E_INVALID, "NULL argument");

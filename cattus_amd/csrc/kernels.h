@@ -113,6 +113,16 @@ bool wino4_tower_fits(uint32_t bpad, uint32_t filters, uint32_t cus);
 void launch_tower_wino4(const Wino4TowerLayer* d_layers, uint32_t nlayers, unsigned* ready, unsigned* err, unsigned* sat, uint32_t bpad, uint32_t filters,
                         uint32_t spin_budget, uint32_t cus, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop);
 
+// ---- calibration: the range of one stream tensor of the f32 per-layer tower (cattus_hip_stream_range) ----
+// rows: plain f32 [nb * slots][FP] (nb * slots % 256 == 0, FP % 64 == 0), of which board < n and pixel slot < S * S are live.  Adds,
+// per channel, the live values' sum of squares to acc_sq [FP] (double) and folds their largest |value| into acc_max [FP] -- the
+// caller zeroes both once and they collect tensor after tensor, ordered by `st`.  part_sq / part_max: scratch of
+// stream_range_parts(bpad, S) * FP entries (bpad >= nb), the workgroups' partials, folded in index order by a second launch: the
+// same bits on every run, no floating-point atomics.
+size_t stream_range_parts(uint32_t bpad, uint32_t S);
+void launch_stream_range(const float* rows, uint32_t nb, uint32_t n, uint32_t S, uint32_t FP, double* part_sq, float* part_max, double* acc_sq,
+                         float* acc_max, hipStream_t st);
+
 // Diagnostic: one launch of nothing but back-to-back MFMAs of the tower's kind (F16S: f16, BF16, F32: 32x32x2 f32), four
 // waves on each of `cus` workgroups, iters x 4 MFMAs per wave; `out` holds cus * 256 floats.  Returns the launch's FLOPs.
 double launch_mfma_sustain(Act act, int cus, int iters, float* out, hipStream_t st);

@@ -12,6 +12,8 @@
 //   K1g conv3x3_generic                                 same arithmetic, any shape, SIMT f32 (checker; wide heads)
 //   K3  head_conv, K4 + K5 head_fc_pair                 1x1 head convs; value FC1 + FC2 + tanh and policy FC (MFMA)
 //       head_conv1x1, value_fc1, value_fc2_tanh, policy_fc   the same on the generic path (SIMT f32)
+//       stream_range, stream_range_finish                   calibration: per-channel sum of squares and maximum of an f32 stream tensor
+//                                                           (HBM-trivial, once per calibrated evaluator, never per batch)
 //
 // Arithmetic the kernels reproduce: ConvNetV1.forward in eval mode
 // (reference: training/cattus_train/net_utils.py:4-89) on the tensor planes_to_tensor builds
@@ -2549,6 +2551,70 @@ void launch_dense(const float* x, uint32_t x_stride, const float* wt, const floa
     if (epi == DENSE_RELU) hipLaunchKernelGGL(policy_fc_kernel<DENSE_RELU>, grid, block, lds, st, x, x_stride, 0u, wt, bias, b, K, N, y);
     else if (epi == DENSE_TANH) hipLaunchKernelGGL(policy_fc_kernel<DENSE_TANH>, grid, block, lds, st, x, x_stride, 0u, wt, bias, b, K, N, y);
     else hipLaunchKernelGGL(policy_fc_kernel<DENSE_SCRUB>, grid, block, lds, st, x, x_stride, 0u, wt, bias, b, K, N, y);
+}
+
+// ------------------------------------------------------------------------------------------
+// Calibration: the range of the residual stream (cattus_hip_stream_range)
+// ------------------------------------------------------------------------------------------
+// One stream tensor of the f32 per-layer tower, plain f32 [rows][FP]: per channel the sum of squares (in double) and the largest
+// |value| over the live rows -- board < n, pixel slot < hw; the other rows hold whatever the conv kernels left there.  A workgroup
+// takes SR_ROWS rows of one 64-channel chunk: thread = (row lane t / 16, 16-byte vector t % 16), so a wave reads four rows' 256-byte
+// pieces, whole 128-byte lines.  Every sum has a fixed order -- a thread's 16 rows, the 16 row lanes through LDS, then the
+// workgroups' partials in index order (stream_range_finish_kernel) -- so the result is the same bits on every run; no atomics.
+constexpr int SR_ROWS = 256;
+__global__ void __launch_bounds__(256) stream_range_kernel(const float* __restrict__ x, uint32_t n, uint32_t slots, uint32_t hw, uint32_t FP,
+                                                           double* __restrict__ part_sq, float* __restrict__ part_max) {
+    __shared__ double sq[16][64];
+    __shared__ float mx[16][64];
+    const uint32_t cv = threadIdx.x & 15, rl = threadIdx.x >> 4;
+    const uint32_t c0 = blockIdx.y * 64 + cv * 4;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    float m[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (uint32_t it = 0; it < SR_ROWS / 16; it++) {
+        const uint32_t row = blockIdx.x * SR_ROWS + it * 16 + rl;
+        if (row / slots < n && row % slots < hw) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(x + (size_t)row * FP + c0);
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const double d = (double)v[j];
+                s[j] += d * d;
+                m[j] = fmaxf(m[j], fabsf(v[j]));
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) sq[rl][cv * 4 + j] = s[j], mx[rl][cv * 4 + j] = m[j];
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        double ts = 0.0;
+        float tm = 0.0f;
+        for (int r = 0; r < 16; r++) ts += sq[r][threadIdx.x], tm = fmaxf(tm, mx[r][threadIdx.x]);
+        const size_t at = (size_t)blockIdx.x * FP + blockIdx.y * 64 + threadIdx.x;
+        part_sq[at] = ts, part_max[at] = tm;
+    }
+}
+
+// Folds the `parts` workgroup partials of one tensor, in index order, into the per-channel accumulators.
+__global__ void __launch_bounds__(64) stream_range_finish_kernel(const double* __restrict__ part_sq, const float* __restrict__ part_max, uint32_t parts,
+                                                                 uint32_t FP, double* __restrict__ acc_sq, float* __restrict__ acc_max) {
+    const uint32_t c = blockIdx.x * 64 + threadIdx.x;
+    double s = acc_sq[c];
+    float m = acc_max[c];
+    for (uint32_t p = 0; p < parts; p++) s += part_sq[(size_t)p * FP + c], m = fmaxf(m, part_max[(size_t)p * FP + c]);
+    acc_sq[c] = s, acc_max[c] = m;
+}
+
+size_t stream_range_parts(uint32_t bpad, uint32_t S) { return (size_t)bpad * tower_slots(S) / SR_ROWS; }
+
+void launch_stream_range(const float* rows, uint32_t nb, uint32_t n, uint32_t S, uint32_t FP, double* part_sq, float* part_max, double* acc_sq,
+                         float* acc_max, hipStream_t st) {
+    const uint32_t slots = tower_slots(S), parts = nb * slots / SR_ROWS;
+    if (nb * slots % SR_ROWS != 0 || FP % 64 != 0 || n > nb) {  // whole workgroups of rows and of channels: the tuned towers' padding
+        fprintf(stderr, "cattus: launch_stream_range: %u boards of %u slots x %u channels, %u leaves\n", nb, slots, FP, n);
+        abort();
+    }
+    hipLaunchKernelGGL(stream_range_kernel, dim3(parts, FP / 64), dim3(256), 0, st, rows, n, slots, S * S, FP, part_sq, part_max);
+    hipLaunchKernelGGL(stream_range_finish_kernel, dim3(FP / 64), dim3(64), 0, st, part_sq, part_max, parts, FP, acc_sq, acc_max);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -71,6 +71,21 @@ inline std::vector<int> stream_shifts(const std::vector<double>& s2) {
     return tk;
 }
 
+// The same shifts from measurement (cattus_hip_create_calibrated): s2_measured[k] is the mean square of stream channel k over sample
+// positions, taken on the exact f32 tower, abs_max[k] its largest |value| there -- what the gamma / beta sums only estimate (they miss
+// a scale carried by the conv rows or the running statistics).  The rule is stream_shifts, fed with the measured mean squares; then a
+// headroom guard, which the estimate has nothing to apply to: while t_k > 0 and abs_max[k] 2^t_k > STREAM_CAL_HEADROOM, t_k drops by
+// one.  4096 = 2^12 is a quarter of the Winograd form's cap (WINO_ACT_MAX, 16376): a factor of four for positions outside the
+// sample.  The guard stops at 0 -- a stream is never shifted down -- so a guarded t_k can lie below the global shift, which stays
+// stream_shift_global(s2_measured).
+constexpr double STREAM_CAL_HEADROOM = 4096.0;
+inline std::vector<int> calibrated_stream_shifts(const std::vector<double>& s2_measured, const std::vector<double>& abs_max) {
+    std::vector<int> tk = stream_shifts(s2_measured);
+    for (size_t k = 0; k < tk.size() && k < abs_max.size(); k++)
+        while (tk[k] > 0 && ldexp(abs_max[k], tk[k]) > STREAM_CAL_HEADROOM) tk[k]--;
+    return tk;
+}
+
 // [cout_pad biases | cout_pad inverse scales 2^-shift]; without shifts (f32, bf16) the biases alone
 inline std::vector<float> bias_and_scales(const Folded& f, const ConvShape& s, const std::vector<int>* shift = nullptr) {
     std::vector<float> b((size_t)(shift ? 2 : 1) * s.cout_pad, 0.0f);

@@ -51,7 +51,10 @@ ABI_SYMBOLS = [
     "cattus_hip_version",
     "cattus_hip_runtime_note",
     "cattus_hip_tower_kernel",
+    "cattus_hip_stream_range",
+    "cattus_hip_create_calibrated",
     "cattus_hip_create_diag",  # include/cattus_hip_diag.h
+    "cattus_hip_create_calibrated_diag",  # include/cattus_hip_diag.h
     "cattus_hip_stream_shift",  # include/cattus_hip_diag.h
     "cattus_hip_stream_shifts",  # include/cattus_hip_diag.h
     "cattus_hip_stem_input",  # include/cattus_hip_diag.h
@@ -96,6 +99,10 @@ class Stats(C.Structure):
     ]
 
 
+class ChannelRange(C.Structure):
+    _fields_ = [("rms", C.c_float), ("abs_max", C.c_float)]
+
+
 class NetDescC(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("planes", "board", "moves", "blocks", "filters", "vhc", "phc", "fc_hidden")]
 
@@ -118,6 +125,9 @@ def load_library():
     vp = C.c_void_p
     L.cattus_hip_create.argtypes = [vp, C.c_size_t, C.POINTER(EvalConfig), C.POINTER(vp)]
     L.cattus_hip_create_diag.argtypes = [vp, C.c_size_t, C.POINTER(EvalConfig), C.c_char_p, C.POINTER(vp)]
+    L.cattus_hip_create_calibrated.argtypes = [vp, C.c_size_t, C.POINTER(EvalConfig), u64p, C.c_uint32, C.POINTER(vp)]
+    L.cattus_hip_create_calibrated_diag.argtypes = [vp, C.c_size_t, C.POINTER(EvalConfig), C.c_char_p, u64p, C.c_uint32, C.POINTER(vp)]
+    L.cattus_hip_stream_range.argtypes = [vp, u64p, C.c_uint32, C.POINTER(ChannelRange), C.c_uint32]
     L.cattus_hip_destroy.argtypes = [vp]
     L.cattus_hip_destroy.restype = None
     L.cattus_hip_desc.argtypes = [vp, C.POINTER(NetDescC)]
@@ -200,10 +210,13 @@ class HipEvaluator:
         flush_us: int = 200,
         tower_form: str | None = None,
         switches: dict | None = None,
+        calibration=None,
     ):
         """tower_form: "auto" | "direct" | "winograd" (cattus_tower_form; None = "auto", or what CATTUS_WINOGRAD=0/1 in the
         environment says).  switches: diagnostic switches for cattus_hip_create_diag (None = the CATTUS_* ones found in the
-        environment, {} = none)."""
+        environment, {} = none).  calibration: sample positions, uint64 ``[n, C, plane_words]`` -- the f16 / f16x2 towers then
+        take their stream shifts from the range measured on them instead of from the BatchNorm parameters
+        (cattus_hip_create_calibrated; nothing to calibrate for f32 / bf16, which come out as without it)."""
         self.desc: NetDesc = parse_header(blob)
         self.batch_size = int(batch_size)
         self.plane_words = int(plane_words)
@@ -221,8 +234,14 @@ class HipEvaluator:
         cfg = EvalConfig(C.sizeof(EvalConfig), device, self.batch_size, self.plane_words, _DTYPES[dtype], flush_us, TOWER_FORMS[tower_form])
         h = C.c_void_p()
         buf = C.create_string_buffer(blob, len(blob))
-        if switches:
-            text = ";".join(f"{k}={v}" for k, v in switches.items()).encode()
+        text = ";".join(f"{k}={v}" for k, v in switches.items()).encode() if switches else None
+        if calibration is not None:
+            cal = self._planes(calibration)
+            if text:
+                _check(self._lib.cattus_hip_create_calibrated_diag(buf, len(blob), C.byref(cfg), text, _u64(cal), len(cal), C.byref(h)))
+            else:
+                _check(self._lib.cattus_hip_create_calibrated(buf, len(blob), C.byref(cfg), _u64(cal), len(cal), C.byref(h)))
+        elif text:
             _check(self._lib.cattus_hip_create_diag(buf, len(blob), C.byref(cfg), text, C.byref(h)))
         else:
             _check(self._lib.cattus_hip_create(buf, len(blob), C.byref(cfg), C.byref(h)))
@@ -328,10 +347,21 @@ class HipEvaluator:
         return self._lib.cattus_hip_stream_shift(self._h)
 
     def stream_shifts(self) -> np.ndarray:
-        """t_k per stream channel (filters entries, each >= stream_shift(); include/cattus_hip_diag.h)."""
+        """t_k per stream channel (filters entries, each >= stream_shift() unless calibration's headroom guard lowered it;
+        include/cattus_hip_diag.h)."""
         out = np.zeros(self.desc.filters, dtype=np.intc)
         _check(self._lib.cattus_hip_stream_shifts(self._h, out.ctypes.data_as(C.POINTER(C.c_int)), len(out)))
         return out
+
+    def stream_range(self, planes) -> tuple[np.ndarray, np.ndarray]:
+        """(rms ``[filters]``, abs_max ``[filters]``) of the residual stream's channels over the leaves ``planes`` (any number: walked
+        in chunks of batch_size), their pixels and the 1 + blocks stream tensors, measured on the exact f32 tower: a dtype f32
+        evaluator only (cattus_hip_stream_range)."""
+        planes = self._planes(planes)
+        out = (ChannelRange * self.desc.filters)()
+        _check(self._lib.cattus_hip_stream_range(self._h, _u64(planes), planes.shape[0], out, self.desc.filters))
+        a = np.frombuffer(out, dtype=np.float32).reshape(-1, 2)
+        return a[:, 0].copy(), a[:, 1].copy()
 
     def stem_input(self) -> tuple[int, bool]:
         """(input channels of the stem conv as laid out on the device, whether the plane pack runs as its own launch in front of it):

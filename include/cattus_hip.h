@@ -103,6 +103,29 @@ int cattus_hip_create(const void* weights, size_t nbytes, const cattus_eval_conf
 void cattus_hip_destroy(cattus_eval* e);
 int cattus_hip_desc(const cattus_eval* e, cattus_net_desc* out);
 
+/* Calibration of the f16 / f16x2 towers on sample positions.  Those towers carry channel k of the residual stream (the stem output
+ * and every block's output) at 2^t_k times its size, so that a small channel keeps its 22 significant bits.  cattus_hip_create
+ * takes t_k from an estimate of the channel's RMS, the BatchNorm gamma / beta that write the stream; that is exact only while
+ * every BatchNorm input has unit variance under its running statistics.  A converted checkpoint whose scale sits elsewhere -- in
+ * the conv rows and running means, say -- is estimated at O(1) whatever its stream does.  These two entry points measure instead.
+ *
+ * cattus_hip_stream_range: rms and largest |value| of every stream channel over the n leaves' S x S pixels and the 1 + blocks
+ * stream tensors, measured on the exact f32 tower.  `e` must be a dtype f32 evaluator on the MFMA per-layer tower (value + policy
+ * head channels <= 32), anything else is CATTUS_E_UNSUPPORTED; channels must be the network's filters and n >= 1, else
+ * CATTUS_E_INVALID.  Any n: the call walks the leaves in chunks of max_batch.  Blocking; takes a lane as cattus_hip_eval does;
+ * the same leaves give the same bytes on every call (no atomics in the reduction), and later evaluations are not changed by it. */
+typedef struct cattus_channel_range { float rms, abs_max; } cattus_channel_range;
+int cattus_hip_stream_range(cattus_eval* e, const uint64_t* planes, uint32_t n, cattus_channel_range* out, uint32_t channels);
+/* cattus_hip_create with the shifts taken from measurement.  dtype f16x2 / f16: builds a temporary f32 evaluator of the same blob on
+ * cfg->device (max_batch = min(n, 256)), measures the n leaves ([n][planes][plane_words], as cattus_hip_eval takes them), destroys
+ * it, and creates the evaluator exactly as cattus_hip_create does except for the shifts: the same rule fed with the measured mean
+ * squares, then a headroom guard -- t_k drops while abs_max 2^t_k > 4096, a quarter of the Winograd form's cap, never below 0.
+ * dtype f32 / bf16 and SimpleTwoHeadedModel blobs have nothing to calibrate: planes and n are validated (non-NULL, n >= 1) and the
+ * call is cattus_hip_create.  A few hundred positions of real play are plenty; cattus_hip_create_calibrated_diag() and the
+ * read-back of what was chosen are in cattus_hip_diag.h. */
+int cattus_hip_create_calibrated(const void* weights, size_t nbytes, const cattus_eval_config* cfg, const uint64_t* planes, uint32_t n,
+                                 cattus_eval** out);
+
 /* planes_to_tensor + run_net for n leaves, blocking (1 <= n <= max_batch, net/mod.rs:122-127).
  * planes: [n][planes][plane_words] u64 host memory; policy: [n][moves]; value: [n]. */
 int cattus_hip_eval(cattus_eval* e, const uint64_t* planes, uint32_t n, float* policy, float* value);

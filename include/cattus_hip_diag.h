@@ -33,15 +33,21 @@ extern "C" {
  *   CATTUS_STREAM_SHIFT=0   the f16 / f16x2 towers carry the residual stream at its own size, however small (see below) */
 int cattus_hip_create_diag(const void* weights, size_t nbytes, const cattus_eval_config* cfg, const char* switches, cattus_eval** out);
 
+/* cattus_hip_create_calibrated (cattus_hip.h) with the same list of switches. */
+int cattus_hip_create_calibrated_diag(const void* weights, size_t nbytes, const cattus_eval_config* cfg, const char* switches,
+                                      const uint64_t* planes, uint32_t n, cattus_eval** out);
+
 /* The stream shift t >= 0 of an f16 / f16x2 evaluator: its tower carries the residual stream at 2^t times its size, so that a
  * stream the trained BatchNorm parameters make small keeps the split activations' lo halves out of the f16 subnormals (exact
  * power-of-two weight products, chosen once from the network at create time; evaluator.hip, choose_stream_shift).  0 for f32
- * and bf16, for a network whose stream is not small, and under CATTUS_STREAM_SHIFT=0. */
+ * and bf16, for a network whose stream is not small, and under CATTUS_STREAM_SHIFT=0.  A calibrated evaluator
+ * (cattus_hip_create_calibrated) reports the same rule on its measured mean squares. */
 int cattus_hip_stream_shift(const cattus_eval* e);
 
 /* The same per channel: out[k] = t_k >= t, n = the network's filters (anything else: CATTUS_E_INVALID).  Channel k of the stream is
  * carried at 2^t_k times its size; t_k > t where channel k alone is small beside the median one (weight_layout.h, stream_shifts).
- * All 0 wherever cattus_hip_stream_shift is 0 by dtype or switch. */
+ * All 0 wherever cattus_hip_stream_shift is 0 by dtype or switch.  Calibrated: weight_layout.h, calibrated_stream_shifts -- measured
+ * channels, and a headroom guard that may take a t_k below t (never below 0). */
 int cattus_hip_stream_shifts(const cattus_eval* e, int* out, uint32_t n);
 
 /* How the stem conv gets its input.  *channels: its input channels as laid out on the device (the planes padded with zero channels;
