@@ -1,6 +1,6 @@
 // Definitions shared by the kernel translation units: vector types, the MFMA wrappers, the fragment-order index, the split
-// tower's LDS pitch and weight-stage constants, small helpers; and, for their host side, what a kernel family's one list of
-// instances is written with.
+// tower's LDS pitch, tap table and weight-stage constants, the workgroup map over the XCDs, small helpers; and, for their
+// host side, what a kernel family's one list of instances is written with.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -90,6 +90,15 @@ __device__ __forceinline__ void note_saturation(const float (&y)[8], bool valid,
     }
 }
 
+// Logical index of workgroup `block` of a grid of nblk.  Consecutive workgroup ids go round the 8 XCDs; the tiled kernels count
+// (row block, cout block) with the cout block fastest, so this map gives every XCD one contiguous range of logical indices: all
+// cout blocks of a range of boards run on one XCD and find their shared rows in its L2.  Grids that are no multiple of 8 stay as
+// they are.  (I: blockIdx.x's unsigned, or the int of a workgroup that walks several grids.)
+template <typename I>
+__device__ __forceinline__ int xcd_remap(I block, int nblk) {
+    return (nblk & 7) == 0 ? (block & 7) * (nblk >> 3) + (block >> 3) : block;
+}
+
 __device__ __forceinline__ void glds16(const char* src, char* lds_dst) {
     __builtin_amdgcn_global_load_lds(GLOBAL_PTR(src), LDS_PTR(lds_dst), 16, 0, 0);
 }
@@ -105,6 +114,27 @@ constexpr int SP = 144;                                 // LDS row pitch
 constexpr int SW_D = 6;                       // weight stages in flight per consumer wave; divides the 18 stages of a chunk
 constexpr int SW_STAGE = 2048;                // bytes per 32-cout block and stage: hi fragment, lo fragment
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+
+// Tap table of a consumer lane on images of SP-byte rows.  rowa[tap][pb]: byte offset, inside an image, of the row that tap reads
+// for the lane's pixel pslot0 + pb * 32 + r of the board whose rows start at image row board_row, plus the lane half's 16 bytes;
+// the image's zero area (at `zero`, above) for a tap off the board or a pixel slot past it.  Loop-invariant: a step adds the
+// image's base, and tap, k-slice and hi / lo fold into ds_read immediates.
+template <int NPB>
+__device__ __forceinline__ void sp_tap_rows(int (&rowa)[9][NPB], int board_row, int pslot0, int r, int h, int S, int zero) {
+#pragma unroll
+    for (int pb = 0; pb < NPB; pb++) {
+        const int p = pslot0 + pb * 32 + r;
+        const int ph = p / S, pw = p - ph * S;
+        const bool pvalid = p < S * S;
+#pragma unroll
+        for (int t9 = 0; t9 < 9; t9++) {
+            const int hh = ph + t9 / 3 - 1, ww = pw + t9 % 3 - 1;
+            const bool ok = pvalid && (unsigned)hh < (unsigned)S && (unsigned)ww < (unsigned)S;
+            const int at = (board_row + hh * S + ww) * SP + h * 16;  // off the board: only its low 8 bits are used
+            rowa[t9][pb] = ok ? at : zero + (at & 255);
+        }
+    }
+}
 
 // ---- host side: a kernel family's instances, listed once ----
 // Next to its kernels every templated family has one for_each_* visitor.  It calls f(kernel, ..., template arguments as

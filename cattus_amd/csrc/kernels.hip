@@ -186,7 +186,8 @@ void launch_planes_to_tensor_nchw(const uint64_t* planes, uint32_t n, uint32_t C
 // ---- diagnostic build only (-DCATTUS_STAMPS): per-wave cycle stamps of the v2 tower kernel ------
 #ifdef CATTUS_STAMPS
 __device__ unsigned long long g_stamps[512 * 8 * 8];
-#define STAMP_DECL unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0}
+typedef unsigned long long StampSlots[8];
+#define STAMP_DECL StampSlots st_ = {0, 0, 0, 0, 0, 0, 0, 0}
 #define STAMP(i) st_[i] = __builtin_amdgcn_s_memtime()
 #define STAMP_RT(i) st_[i] = __builtin_amdgcn_s_memrealtime()
 #define STAMP_ACC_BEGIN unsigned long long acc_t0_ = __builtin_amdgcn_s_memtime()
@@ -195,7 +196,8 @@ __device__ unsigned long long g_stamps[512 * 8 * 8];
     if ((threadIdx.x & 63) == 0 && blockIdx.x < 256)                               \
         for (int q_ = 0; q_ < 8; q_++) g_stamps[(blockIdx.x * 16 + (wave)) * 8 + q_] = st_[q_]
 #else
-#define STAMP_DECL
+struct StampSlots {};  // what the helpers below take in place of the stamps
+#define STAMP_DECL [[maybe_unused]] StampSlots st_
 #define STAMP(i)
 #define STAMP_RT(i)
 #define STAMP_ACC_BEGIN
@@ -221,10 +223,7 @@ constexpr int V2_LDS_TOTAL = V2_LDS_ACT + 2 * 32768;  // 139520 B
 static_assert(V2_LDS_ZERO % 256 == 0 && V2_LDS_ACT % 256 == 0, "off-board reads keep their row's banks only if both are 256-B aligned");
 
 
-#ifndef CATTUS_NLOAD
-#define CATTUS_NLOAD 4  // loader waves per workgroup (the kernels assert 4)
-#endif
-constexpr int NLOAD = CATTUS_NLOAD;
+constexpr int NLOAD = 4;         // loader waves per workgroup
 constexpr int WPL = 24 / NLOAD;  // weight pieces per loader wave and step
 constexpr int APL = 16 / NLOAD;  // activation pieces per loader wave and half-chunk
 
@@ -238,6 +237,100 @@ struct StemPlanes<true> {
     const uint64_t* planes;  // [n][C][w64]
     uint32_t n, C, w64;
 };
+
+// ---- parts that the three per-layer kernels share ----
+
+// K0 fused, first half: a loader thread expands pixel row `row` (lw * 64 + lane) of the workgroup's rows.  This requests all plane
+// words of the row's pixel (one round trip; zeros for a row past the workgroup's, the batch's or the board's) and returns the
+// pixel slot; whatever the caller issues next goes out behind them.
+template <bool BIG>
+__device__ __forceinline__ uint32_t stem_row_words(uint64_t (&words)[32], const StemPlanes<true>& sp, int row0, int row, bool row_ok, int S) {
+    const uint32_t grow = (uint32_t)(row0 + row), slots = BIG ? 128u : 64u;
+    const uint32_t board = grow / slots, px = grow % slots;
+    const bool live = row_ok && board < sp.n && (int)px < S * S;
+    typedef const __attribute__((address_space(1))) uint64_t* gu64p;
+    const gu64p pl = (gu64p)(sp.planes + (size_t)(live ? board : 0) * sp.C * sp.w64 + (live ? (px >> 6) : 0));
+#pragma unroll
+    for (int c = 0; c < 32; c++) words[c] = (live && (uint32_t)c < sp.C) ? pl[(size_t)c * sp.w64] : 0ull;
+    return px;
+}
+// Second half: the row's first 128 bytes as elements of T, channel c = 1.0 where plane c has the pixel's bit, channels from 32 on
+// zero (for the f16 pairs of the split tower that is the hi half in slots 0..3 and a zero lo half in slots 4..7).  16-byte slot
+// s lands in slot s ^ swz: the v2 kernel's swizzle of the row, where the LDS-DMA path would have put it, or 0 for the linear rows
+// of a padded image.
+template <typename T>
+__device__ __forceinline__ void stem_row_store(char* dstrow, int swz, const uint64_t (&words)[32], uint32_t px, bool row_ok) {
+    constexpr int VEC = 16 / (int)sizeof(T);  // channels per 16-byte slot
+    constexpr int MAXC = 32;
+#pragma unroll
+    for (int sl = 0; sl < 8; sl++) {
+        T vals[VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; i++) {
+            const int c = sl * VEC + i;
+            vals[i] = (c < MAXC && ((words[c < MAXC ? c : 0] >> (px & 63)) & 1ull)) ? (T)1.0f : (T)0.0f;
+        }
+        if (row_ok) *reinterpret_cast<f32x4*>(dstrow + ((sl ^ swz) << 4)) = *reinterpret_cast<f32x4*>(vals);
+    }
+}
+
+// A loader wave's wait in front of a step's barrier: all but its N youngest loads have landed.  The diagnostic build times the
+// wait for the data (slot 4) and the wait at the barrier (slot 7) apart.
+template <int N>
+__device__ __forceinline__ void loader_wait_vm(StampSlots& st_) {
+#ifdef CATTUS_STAMPS
+    const unsigned long long t0_ = __builtin_amdgcn_s_memtime();
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+    const unsigned long long t1_ = __builtin_amdgcn_s_memtime();
+    asm volatile("s_barrier" ::: "memory");
+    st_[4] += t1_ - t0_;
+    st_[7] += __builtin_amdgcn_s_memtime() - t1_;
+#else
+    wait_vm_barrier<N>();
+#endif
+}
+// The same where the loads issued after the data of the upcoming step are A weight pieces and B activation pieces, A weight
+// pieces alone, or none (the immediate has to be a literal).
+template <int A, int B>
+__device__ __forceinline__ void loader_wait(int pending, StampSlots& st_) {
+    if (pending == A + B) loader_wait_vm<A + B>(st_);
+    else if (pending == A) loader_wait_vm<A>(st_);
+    else loader_wait_vm<0>(st_);
+}
+
+// Epilogue transpose.  The accumulators hold, per lane, 4 consecutive couts of one pixel; written straight to NHWC that is 64
+// 8-byte stores per lane hitting 32 lines each.  Instead the wave transposes its tile through its own (now idle) activation rows
+// in LDS as f32 [px][32 CB couts] (XOR-swizzled 16-byte slots), then every lane owns 8 consecutive couts of one pixel: one skip
+// load and one store of whole 128-byte lines per lane and pixel row.  The staged tile:
+//   CB = 2: 256-byte rows, px 0..31 at tile0, px 32..63 `stride` bytes further (the same rows of the second activation buffer);
+//   CB = 1: 128-byte rows, all of them at tile0.
+template <int CB>
+__device__ __forceinline__ int stage_row(int tile0, int stride, int px) {
+    return CB == 2 ? tile0 + (px >> 5) * stride + (px & 31) * 256 : tile0 + px * 128;
+}
+// addend: nothing, or [CB][4] vectors added to the lane's 4 couts of (cb, g) on the way (the v2 kernel's bias)
+template <int CB, int PBW>
+__device__ __forceinline__ void stage_tile(const f32x16 (&acc)[CB][PBW], char* smem, int tile0, int stride, int r, int h, const f32x4 (*addend)[4] = nullptr) {
+#pragma unroll
+    for (int cb = 0; cb < CB; cb++)
+#pragma unroll
+        for (int pb = 0; pb < PBW; pb++)
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                f32x4 v;
+#pragma unroll
+                for (int i = 0; i < 4; i++) v[i] = addend ? acc[cb][pb][g * 4 + i] + addend[cb][g][i] : acc[cb][pb][g * 4 + i];
+                const int slot = (cb * 8 + g * 2 + h) ^ (r & 7);
+                *reinterpret_cast<f32x4*>(smem + stage_row<CB>(tile0, stride, pb * 32 + r) + slot * 16) = v;
+            }
+}
+// the 8 couts 8 cg .. 8 cg + 7 of staged pixel row px
+__device__ __forceinline__ void staged_read(float (&v)[8], const char* rowp, int px, int cg) {
+    const f32x4 lo = *reinterpret_cast<const f32x4*>(rowp + (((2 * cg) ^ (px & 7)) << 4));
+    const f32x4 hi = *reinterpret_cast<const f32x4*>(rowp + (((2 * cg + 1) ^ (px & 7)) << 4));
+#pragma unroll
+    for (int j = 0; j < 4; j++) v[j] = lo[j], v[4 + j] = hi[j];
+}
 
 // BIG: 128 pixel slots per board (two consumer waves per board).
 // STEM: the layer's input is the bitboard planes (C <= 32 planes, one 128-byte chunk): `in` is not read.
@@ -274,9 +367,7 @@ __global__ void __launch_bounds__(256 + 64 * NLOAD, (4 + NLOAD) / 4)
     STAMP(0);
     STAMP_RT(5);
 
-    const int nblk = gridDim.x, ncb = cout / CPW;
-    int logical = blockIdx.x;
-    if ((nblk & 7) == 0) logical = (blockIdx.x & 7) * (nblk >> 3) + (blockIdx.x >> 3);
+    const int ncb = cout / CPW, logical = xcd_remap(blockIdx.x, gridDim.x);
     const int cout0 = (logical % ncb) * CPW;
     const int row0 = (logical / ncb) * RW;  // first tower row (board * slots + pixel slot) of this workgroup
 
@@ -328,35 +419,13 @@ __global__ void __launch_bounds__(256 + 64 * NLOAD, (4 + NLOAD) / 4)
         };
 
         if constexpr (STEM) {
-            // K0 fused: this thread expands pixel row (lw * 64 + lane) of the workgroup's 256 rows.  All plane words
-            // of its board first (one round trip), the first weight slabs behind them, then the row: channel c of
-            // the row is 1.0 where plane c has the pixel's bit; channel slot s lands in LDS slot s ^ swizzle(row),
-            // where the LDS-DMA path would have put it.
-            constexpr int VEC = 16 / (int)sizeof(T);   // channels per 16-byte slot
-            constexpr int MAXC = 32;
+            // K0 fused: the plane words first, the first weight slabs behind them, then the row
             const int row = lw * 64 + lane;
-            const uint32_t grow = (uint32_t)(row0 + row), slots = BIG ? 128u : 64u;
-            const uint32_t board = grow / slots, px = grow % slots;
-            const bool live = row < RW && board < sp.n && (int)px < S * S;
-            typedef const __attribute__((address_space(1))) uint64_t* gu64p;
-            const gu64p pl = (gu64p)(sp.planes + (size_t)(live ? board : 0) * sp.C * sp.w64 + (live ? (px >> 6) : 0));
-            uint64_t words[MAXC];
-#pragma unroll
-            for (int c = 0; c < MAXC; c++) words[c] = (live && (uint32_t)c < sp.C) ? pl[(size_t)c * sp.w64] : 0ull;
+            uint64_t words[32];
+            const uint32_t px = stem_row_words<BIG>(words, sp, row0, row, row < RW, S);
             issue_w(0);
             issue_w(1);
-            char* dstrow = smem + V2_LDS_ACT + row * 128;
-            const int swz = (row >> 1) & 7;
-#pragma unroll
-            for (int sl = 0; sl < 8; sl++) {
-                T vals[VEC];
-#pragma unroll
-                for (int i = 0; i < VEC; i++) {
-                    const int c = sl * VEC + i;
-                    vals[i] = (c < MAXC && ((words[c < MAXC ? c : 0] >> (px & 63)) & 1ull)) ? (T)1.0f : (T)0.0f;
-                }
-                if (row < RW) *reinterpret_cast<f32x4*>(dstrow + ((sl ^ swz) << 4)) = *reinterpret_cast<f32x4*>(vals);
-            }
+            stem_row_store<T>(smem + V2_LDS_ACT + row * 128, (row >> 1) & 7, words, px, row < RW);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the rows are written before the first barrier
         } else {
             issue_a(0, 0);
@@ -366,22 +435,7 @@ __global__ void __launch_bounds__(256 + 64 * NLOAD, (4 + NLOAD) / 4)
         }
         int pending = WPLC;  // loads issued after the data of the upcoming step
         for (int t = 0; t < T_total; t++) {
-#ifdef CATTUS_STAMPS
-            {  // diagnostic build: time the wait for the data (slot 4) and the wait at the barrier (slot 7) apart
-                const unsigned long long t0_ = __builtin_amdgcn_s_memtime();
-                if (pending == WPLC + APL) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WPLC + APL) : "memory");
-                else if (pending == WPLC) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WPLC) : "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                const unsigned long long t1_ = __builtin_amdgcn_s_memtime();
-                asm volatile("s_barrier" ::: "memory");
-                st_[4] += t1_ - t0_;
-                st_[7] += __builtin_amdgcn_s_memtime() - t1_;
-            }
-#else
-            if (pending == WPLC + APL) wait_vm_barrier<WPLC + APL>();
-            else if (pending == WPLC) wait_vm_barrier<WPLC>();
-            else wait_vm_barrier<0>();
-#endif
+            loader_wait<WPLC, APL>(pending, st_);
             if (t == 0) STAMP(1);
             pending = 0;
             const int ch = t / 3, g = t - ch * 3;
@@ -403,9 +457,6 @@ __global__ void __launch_bounds__(256 + 64 * NLOAD, (4 + NLOAD) / 4)
     }
 
     // ================================ consumer waves ================================
-#ifdef CATTUS_CONSUMER_PRIO
-    __builtin_amdgcn_s_setprio(1);  // MFMA waves win issue arbitration against the loader wave on their SIMD
-#endif
     const int r = lane & 31, h = lane >> 5;
     // pixel slot of this lane's two output columns within its board, and the LDS offset of the board's rows
     constexpr int SLOTS = BIG ? 128 : 64, WPB = SLOTS / PXW;  // consumer waves per board
@@ -486,8 +537,6 @@ __global__ void __launch_bounds__(256 + 64 * NLOAD, (4 + NLOAD) / 4)
             if (ch == 0 && g == 0) STAMP(1);
             // keep the per-step activation addresses from being hoisted out of the chunk loop (72 VGPRs)
             asm volatile("" : "+v"(opaque));
-            constexpr int dummy = 0;
-            (void)dummy;
             const int wslab = g * V2_SLAB;  // ring slot of step ch*3+g is g
             int baddr[3][PBW][4];
 #pragma unroll
@@ -529,12 +578,7 @@ __global__ void __launch_bounds__(256 + 64 * NLOAD, (4 + NLOAD) / 4)
         }
     }
 
-    // ---- epilogue ----
-    // The accumulators hold, per lane, 4 consecutive couts of one pixel; written straight to NHWC
-    // that is 64 8-byte stores per lane hitting 32 lines each.  Instead the wave transposes its
-    // 64 px x 64 cout tile through its own (now idle) activation LDS region as f32 [px][64 cout]
-    // (XOR-swizzled 16-byte slots), then every lane owns 8 consecutive couts of one pixel: one
-    // 16/32-byte residual load and one 16/32-byte store per lane and pixel row, whole 128-byte lines.
+    // ---- epilogue: transpose (stage_tile), then per lane 8 consecutive couts of one pixel ----
     STAMP(2);
     if (MEET) {
         // the staging region below holds pixel rows the OTHER wave of this board may still be reading as
@@ -557,34 +601,12 @@ __global__ void __launch_bounds__(256 + 64 * NLOAD, (4 + NLOAD) / 4)
                 }
             }
         }
-        // staged tile: CB = 2: f32 [px][64 couts] = 256-byte rows, px 0..31 at tile0, px 32..63 32768 bytes further;
-        //              CB = 1: f32 [px][32 couts] = 128-byte rows, all 64 at tile0
-        auto stage_row = [&](int px) { return CB == 2 ? tile0 + (px >> 5) * 32768 + (px & 31) * 256 : tile0 + px * 128; };
-#pragma unroll
-        for (int cb = 0; cb < CB; cb++)
-#pragma unroll
-            for (int pb = 0; pb < PBW; pb++)
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    f32x4 v;
-                    if constexpr (F16T) {
-#pragma unroll
-                        for (int i = 0; i < 4; i++) v[i] = acc[cb][pb][g * 4 + i];
-                    } else {
-                        const f32x4 bv = biasv[cb][g];
-#pragma unroll
-                        for (int i = 0; i < 4; i++) v[i] = acc[cb][pb][g * 4 + i] + bv[i];
-                    }
-                    const int slot = (cb * 8 + g * 2 + h) ^ (r & 7);
-                    *reinterpret_cast<f32x4*>(smem + stage_row(pb * 32 + r) + slot * 16) = v;
-                }
+        stage_tile<CB, PBW>(acc, smem, tile0, 32768, r, h, F16T ? nullptr : biasv);  // f16: the bias follows the inverse scale
 #pragma unroll
         for (int i = 0; i < EIT; i++) {
             const int px = i * RPT + prow;
-            const char* rowp = smem + stage_row(px);
-            const f32x4 lo = *reinterpret_cast<const f32x4*>(rowp + (((2 * cg) ^ (px & 7)) << 4));
-            const f32x4 hi = *reinterpret_cast<const f32x4*>(rowp + (((2 * cg + 1) ^ (px & 7)) << 4));
-            float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            float v[8];
+            staged_read(v, smem + stage_row<CB>(tile0, 32768, px), px, cg);
             const size_t off = (wrow0 + px) * (size_t)cout + cout0 + cg * 8;
             if constexpr (F16T) {  // the accumulator carries the weights' power-of-two scale: times its inverse is exact
 #pragma unroll
@@ -687,6 +709,94 @@ constexpr int SP_LDS_TOTAL = SP_LDS_ACT + 2 * SP_ABUF;  // 157,376 B
 static_assert(SP_ZERO % 256 == 0, "off-board reads keep their row's banks only if the zero area is 256-B aligned inside the buffer");
 constexpr int SP_WPL = 7, SP_APL = 5;                   // pieces per loader wave: 28 >= 27 per slab, 20 >= 18 per half chunk
 
+// ---- parts that the two split kernels share ----
+
+// The loader waves build a padded image (rows of SP bytes) from dense 128-byte global rows, 1 KiB LDS-DMA pieces at a time: piece
+// `pid` fills image bytes [pid * 1024, +1024), lane l writing 16-byte slot pid * 64 + l of the image, i.e. slot c = that % 9 of
+// image row that / 9; slot 8 is the padding (it re-reads slot 7).
+__device__ __forceinline__ void sp_piece_slot(int pid, int lane, int& irow, int& c) {
+    const int sidx = pid * 64 + lane;
+    irow = sidx / 9;
+    c = min(sidx - irow * 9, 7);
+}
+// Loader wave lw's SP_APL pieces of each half (128 rows = 18 pieces) of an activation chunk: source offset from the chunk's
+// first row, destination offset in the buffer.  A wave's surplus pieces repeat the half's last piece, so every wave issues the
+// same count and the vmcnt arithmetic stays uniform.
+template <int NHALF>
+__device__ __forceinline__ void sp_image_pieces(uint32_t (&off_a)[NHALF][SP_APL], int (&dst_a)[NHALF][SP_APL], int lw, int lane, uint32_t row_bytes) {
+#pragma unroll
+    for (int g = 0; g < NHALF; g++)
+#pragma unroll
+        for (int i = 0; i < SP_APL; i++) {
+            const int id = g * 18 + min(lw * SP_APL + i, 17);
+            int irow, c;
+            sp_piece_slot(id, lane, irow, c);
+            off_a[g][i] = (uint32_t)irow * row_bytes + c * 16;
+            dst_a[g][i] = id * 1024;
+        }
+}
+
+// Rows of `in` / `res` / `out`: 4 bytes per channel, the hi values of cout c at element sp_col(c), the lo values 32 further.
+__device__ __forceinline__ int sp_col(int c) { return (c >> 5) * 64 + (c & 31); }
+
+// One staged pixel row (stage_tile) to its stores: the lane's 8 couts from `col` on of tower row `row`.  Times the inverse weight
+// scale plus bias (the accumulator carries the weights' power-of-two scale, so the product is exact and the fused multiply-add
+// rounds as a multiply followed by an add would), + skip as hi + lo (exact in f32: lo is at most half an ulp of hi, 22 significant
+// bits), ReLU, then either plain f32 rows (flags & CONV_OUT_F32: the tower's last layer, for the head kernels or a Winograd
+// tower's stem) or the clamp at 65504 and the split into (hi, lo).  Pixel slots past the board (!valid) stay zero: masked once,
+// on the packed vectors.  Stores: non-temporal on the full grid (CB = 2), where a layer's 16.7 MB of output and its 2.4 MB of
+// weights do not fit the XCDs' L2 together; plain on the small-grid tile (CB = 1, <= 128 leaves of an 8x8 game), where the output
+// stays in the L2 of the XCD whose workgroups read it back as the next layer's input (xcd_remap keeps a row block on one XCD):
+// 18.5 us per launch against 19.9 with non-temporal stores at batch 64, no difference at 128.
+template <int CB, bool HAS_RES>
+__device__ __forceinline__ void finish_f16x2(const char* rowp, int px, int cg, const f32x4 (&ds8)[2], const f32x4 (&bias8)[2],
+                                             const _Float16 (&resv)[16], bool valid, int flags, unsigned* sat, _Float16* out, size_t row,
+                                             int cout, int col) {
+    typedef _Float16 T;
+    float v[8];
+    staged_read(v, rowp, px, cg);
+#pragma unroll
+    for (int j = 0; j < 8; j++) v[j] = __builtin_fmaf(v[j], ds8[j >> 2][j & 3], bias8[j >> 2][j & 3]);
+    if (HAS_RES) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) v[j] = v[j] + ((float)resv[j] + (float)resv[8 + j]);
+    }
+    float y[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) y[j] = v[j] > 0.0f ? v[j] : 0.0f;
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    if (flags & CONV_OUT_F32) {
+        if (flags & CONV_WINO_IN) cap_wino_input(y, valid, sat);
+        float* of = reinterpret_cast<float*>(out) + row * (size_t)cout + col;
+        const f32x4 y0 = valid ? *reinterpret_cast<f32x4*>(y) : zero4, y1 = valid ? *reinterpret_cast<f32x4*>(y + 4) : zero4;
+        if constexpr (CB == 2) {
+            __builtin_nontemporal_store(y0, reinterpret_cast<f32x4*>(of));
+            __builtin_nontemporal_store(y1, reinterpret_cast<f32x4*>(of) + 1);
+        } else {
+            reinterpret_cast<f32x4*>(of)[0] = y0;
+            reinterpret_cast<f32x4*>(of)[1] = y1;
+        }
+    } else {
+        const size_t off = row * ((size_t)cout * 2) + sp_col(col);
+        T hi[8], lo[8];
+        note_saturation(y, valid, sat);
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const float yc = y[j] < 65504.0f ? y[j] : 65504.0f;  // saturate instead of overflowing to infinity
+            hi[j] = (T)yc;
+            lo[j] = (T)(yc - (float)hi[j]);
+        }
+        const f32x4 hi4o = valid ? *reinterpret_cast<f32x4*>(hi) : zero4, lo4o = valid ? *reinterpret_cast<f32x4*>(lo) : zero4;
+        if constexpr (CB == 2) {
+            __builtin_nontemporal_store(hi4o, reinterpret_cast<f32x4*>(out + off));
+            __builtin_nontemporal_store(lo4o, reinterpret_cast<f32x4*>(out + off + 32));
+        } else {
+            *reinterpret_cast<f32x4*>(out + off) = hi4o;
+            *reinterpret_cast<f32x4*>(out + off + 32) = lo4o;
+        }
+    }
+}
+
 template <bool HAS_RES, bool BIG, bool STEM, int CB>
 __global__ void __launch_bounds__(512, 2)
     conv3x3_split_kernel(const _Float16* __restrict__ in, const _Float16* __restrict__ w, const float* __restrict__ bias,
@@ -706,9 +816,7 @@ __global__ void __launch_bounds__(512, 2)
     STAMP(0);
     STAMP_RT(5);
 
-    const int nblk = gridDim.x, ncb = cout / CPW;
-    int logical = blockIdx.x;
-    if ((nblk & 7) == 0) logical = (blockIdx.x & 7) * (nblk >> 3) + (blockIdx.x >> 3);
+    const int ncb = cout / CPW, logical = xcd_remap(blockIdx.x, gridDim.x);
     const int cout0 = (logical % ncb) * CPW;
     const int row0 = (logical / ncb) * ROWS_PER_WG;
 
@@ -722,29 +830,20 @@ __global__ void __launch_bounds__(512, 2)
 
     if (is_loader) {
         // ================================ loader waves ================================
-        // Piece `pid` fills image bytes [pid * 1024, +1024): lane l writes 16-byte slot pid * 64 + l of the image, i.e. slot
-        // c = that % 9 of image row that / 9; slot 8 is the padding (it re-reads slot 7).  A wave's surplus pieces repeat
-        // the image's last piece, so every wave issues the same count and the vmcnt arithmetic below stays uniform.
+        // the weight slab is a padded image like the activation chunk (sp_piece_slot); surplus pieces repeat its last one
         const int lw = wave - 4;
         uint32_t off_w[SP_WPL], off_a[2][SP_APL];
         int dst_w[SP_WPL], dst_a[2][SP_APL];
 #pragma unroll
         for (int i = 0; i < SP_WPL; i++) {
             const int pid = min(lw * SP_WPL + i, 26);
-            const int sidx = pid * 64 + lane, irow = sidx / 9, c = min(sidx - irow * 9, 7);
+            int irow, c;
+            sp_piece_slot(pid, lane, irow, c);
             const int tap_i = irow >> 6, row = CB == 2 ? (irow & 63) : (irow & 31);  // CB = 1: rows 32..63 of a tap are not read
             off_w[i] = ((uint32_t)(tap_i * cout + row)) * row_bytes + c * 16;
             dst_w[i] = pid * 1024;
         }
-#pragma unroll
-        for (int g = 0; g < 2; g++)
-#pragma unroll
-            for (int i = 0; i < SP_APL; i++) {
-                const int id = g * 18 + min(lw * SP_APL + i, 17);
-                const int sidx = id * 64 + lane, irow = sidx / 9, c = min(sidx - irow * 9, 7);
-                off_a[g][i] = (uint32_t)irow * row_bytes + c * 16;
-                dst_a[g][i] = id * 1024;
-            }
+        sp_image_pieces<2>(off_a, dst_a, lw, lane, row_bytes);
         const char* wbase0 = reinterpret_cast<const char*>(w) + (size_t)cout0 * row_bytes;
         const char* abase0 = reinterpret_cast<const char*>(in) + (size_t)row0 * row_bytes;
         auto issue_w = [&](int t) {  // weight slab of step t -> ring slot t % 3
@@ -762,31 +861,13 @@ __global__ void __launch_bounds__(512, 2)
         };
 
         if constexpr (STEM) {
-            // K0 fused: this thread expands pixel row (lw * 64 + lane) of the workgroup's 256 rows: channel c of the row is 1.0
-            // where plane c has the pixel's bit (hi half, slots 0..3); the lo half (slots 4..7) is zero
-            constexpr int MAXC = 32;
+            // K0 fused: the plane words first, the first weight slabs behind them, then the row
             const int row = lw * 64 + lane;
-            const uint32_t grow = (uint32_t)(row0 + row), slots = BIG ? 128u : 64u;
-            const uint32_t board = grow / slots, px = grow % slots;
-            const bool live = board < sp.n && (int)px < S * S;
-            typedef const __attribute__((address_space(1))) uint64_t* gu64p;
-            const gu64p pl = (gu64p)(sp.planes + (size_t)(live ? board : 0) * sp.C * sp.w64 + (live ? (px >> 6) : 0));
-            uint64_t words[MAXC];
-#pragma unroll
-            for (int c = 0; c < MAXC; c++) words[c] = (live && (uint32_t)c < sp.C) ? pl[(size_t)c * sp.w64] : 0ull;
+            uint64_t words[32];
+            const uint32_t px = stem_row_words<BIG>(words, sp, row0, row, true, S);
             issue_w(0);
             issue_w(1);
-            char* dstrow = smem + SP_LDS_ACT + row * SP;
-#pragma unroll
-            for (int sl = 0; sl < 8; sl++) {
-                T vals[8];
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    const int c = sl * 8 + i;
-                    vals[i] = (c < MAXC && ((words[c < MAXC ? c : 0] >> (px & 63)) & 1ull)) ? (T)1.0f : (T)0.0f;
-                }
-                *reinterpret_cast<f32x4*>(dstrow + sl * 16) = *reinterpret_cast<f32x4*>(vals);
-            }
+            stem_row_store<T>(smem + SP_LDS_ACT + row * SP, 0, words, px, true);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the rows are written before the first barrier
         } else {
             issue_a(0, 0);
@@ -796,22 +877,7 @@ __global__ void __launch_bounds__(512, 2)
         }
         int pending = SP_WPL;  // loads issued after the data of the upcoming step
         for (int t = 0; t < T_total; t++) {
-            {
-#ifdef CATTUS_STAMPS
-                const unsigned long long t0_ = __builtin_amdgcn_s_memtime();
-                if (pending == SP_WPL + SP_APL) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SP_WPL + SP_APL) : "memory");
-                else if (pending == SP_WPL) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SP_WPL) : "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                const unsigned long long t1_ = __builtin_amdgcn_s_memtime();
-                asm volatile("s_barrier" ::: "memory");
-                st_[4] += t1_ - t0_;
-                st_[7] += __builtin_amdgcn_s_memtime() - t1_;
-#else
-                if (pending == SP_WPL + SP_APL) wait_vm_barrier<SP_WPL + SP_APL>();
-                else if (pending == SP_WPL) wait_vm_barrier<SP_WPL>();
-                else wait_vm_barrier<0>();
-#endif
-            }
+            loader_wait<SP_WPL, SP_APL>(pending, st_);
             if (t == 0) STAMP(1);
             pending = 0;
             const int ch = t / 3, g = t - ch * 3;
@@ -836,22 +902,8 @@ __global__ void __launch_bounds__(512, 2)
     const int r = lane & 31, h = lane >> 5;
     const int pslot0 = BIG ? (wave & 1) * 64 : 0;
     const int board_row = BIG ? (wave >> 1) * 128 : wave * 64;  // first LDS row of this wave's board
-    // Byte offset, inside an activation buffer, of the row each tap reads for this lane's two pixels (the buffer's zero
-    // row for a tap off the board), plus the lane half's 16 bytes: loop-invariant; a step adds the buffer's base.
     int rowa[9][2];
-#pragma unroll
-    for (int pb = 0; pb < 2; pb++) {
-        const int p = pslot0 + pb * 32 + r;
-        const int ph = p / S, pw = p - ph * S;
-        const bool pvalid = p < S * S;
-#pragma unroll
-        for (int t9 = 0; t9 < 9; t9++) {
-            const int hh = ph + t9 / 3 - 1, ww = pw + t9 % 3 - 1;
-            const bool ok = pvalid && (unsigned)hh < (unsigned)S && (unsigned)ww < (unsigned)S;
-            const int at = (board_row + hh * S + ww) * SP + h * 16;  // off the board: only its low 8 bits are used
-            rowa[t9][pb] = ok ? at : SP_ZERO + (at & 255);
-        }
-    }
+    sp_tap_rows<2>(rowa, board_row, pslot0, r, h, S, SP_ZERO);
     int aaddr[CB];
 #pragma unroll
     for (int cb = 0; cb < CB; cb++) aaddr[cb] = (cb * 32 + r) * SP + h * 16;
@@ -874,8 +926,8 @@ __global__ void __launch_bounds__(512, 2)
         bias8[q] = *reinterpret_cast<const f32x4*>(bias + cout0 + cg * 8 + q * 4);
         ds8[q] = *reinterpret_cast<const f32x4*>(bias + cout + cout0 + cg * 8 + q * 4);
     }
-    const size_t orow = (size_t)cout * 2;  // elements of T per row of `res` / `out`
-    const int ocol = ((cout0 + cg * 8) >> 5) * 64 + ((cout0 + cg * 8) & 31);  // hi values of the lane's 8 couts; lo 32 further
+    const size_t orow = (size_t)cout * 2;  // elements of T per row of `res`
+    const int ocol = sp_col(cout0 + cg * 8);
     // The skip rows (64 KiB per workgroup) are requested behind the first barrier, not here: the prologue is a burst of
     // ~90 KiB per CU that every workgroup of the chip issues at once, and these have the whole loop to arrive (measured
     // against requesting them here: no difference, 1.770 vs 1.773 ms per batch; profiles/r03_experiments.txt).
@@ -945,68 +997,18 @@ __global__ void __launch_bounds__(512, 2)
         }
     }
 
-    // ---- epilogue: transpose through the wave's own (idle) activation rows as in conv3x3_mfma_v2_kernel, then per lane 8
-    // consecutive couts of one pixel: * inverse scale + bias, + skip, ReLU, split into (hi, lo), two 16-byte stores ----
+    // ---- epilogue: transpose through the wave's own rows of the two buffers (stage_tile), then finish_f16x2 per pixel row ----
     STAMP(2);
     if (BIG) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // the board's other wave may still read these rows
     {
         const size_t wrow0 = (size_t)row0 + wave * 64;
         const int tile0 = SP_LDS_ACT + wave * 64 * SP;  // the wave's 64 rows of buffer 0 (9,216 B); the same rows of buffer 1 behind
-        // staged tile: CB = 2: f32 [px][64 couts] = 256-byte rows, px 0..31 in buffer 0, px 32..63 in buffer 1;
-        //              CB = 1: f32 [px][32 couts] = 128-byte rows, all 64 in buffer 0
-        auto stage_row = [&](int px) { return CB == 2 ? tile0 + (px >> 5) * SP_ABUF + (px & 31) * 256 : tile0 + px * 128; };
-#pragma unroll
-        for (int cb = 0; cb < CB; cb++)
-#pragma unroll
-            for (int pb = 0; pb < 2; pb++)
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    f32x4 v;
-#pragma unroll
-                    for (int i = 0; i < 4; i++) v[i] = acc[cb][pb][g * 4 + i];
-                    const int slot = (cb * 8 + g * 2 + h) ^ (r & 7);
-                    *reinterpret_cast<f32x4*>(smem + stage_row(pb * 32 + r) + slot * 16) = v;
-                }
+        stage_tile<CB, 2>(acc, smem, tile0, SP_ABUF, r, h);
 #pragma unroll
         for (int i = 0; i < EIT; i++) {
             const int px = i * RPT + prow;
-            const char* rowp = smem + stage_row(px);
-            const f32x4 lo4 = *reinterpret_cast<const f32x4*>(rowp + (((2 * cg) ^ (px & 7)) << 4));
-            const f32x4 hi4 = *reinterpret_cast<const f32x4*>(rowp + (((2 * cg + 1) ^ (px & 7)) << 4));
-            float v[8] = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-            // the accumulator carries the weights' power-of-two scale: times its inverse is exact
-#pragma unroll
-            for (int j = 0; j < 8; j++) v[j] = v[j] * ds8[j >> 2][j & 3] + bias8[j >> 2][j & 3];
-            if (HAS_RES) {
-                // hi + lo is exact in f32 (lo is at most half an ulp of hi: 22 significant bits)
-#pragma unroll
-                for (int j = 0; j < 8; j++) v[j] = v[j] + ((float)resv[i][j] + (float)resv[i][8 + j]);
-            }
-            const bool valid = pslot0 + px < S * S;
-            float y[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                y[j] = v[j] > 0.0f ? v[j] : 0.0f;
-                if (!valid) y[j] = 0.0f;
-            }
-            if (flags & CONV_OUT_F32) {  // the tower's last layer: plain f32 rows for the head kernels (or a Winograd tower's stem)
-                if (flags & CONV_WINO_IN) cap_wino_input(y, true, sat);
-                float* of = reinterpret_cast<float*>(out) + (wrow0 + px) * (size_t)cout + cout0 + cg * 8;
-                __builtin_nontemporal_store(*reinterpret_cast<f32x4*>(y), reinterpret_cast<f32x4*>(of));
-                __builtin_nontemporal_store(*reinterpret_cast<f32x4*>(y + 4), reinterpret_cast<f32x4*>(of) + 1);
-            } else {
-                const size_t off = (wrow0 + px) * orow + ocol;
-                T hi[8], lo[8];
-                note_saturation(y, true, sat);  // rows past the board are zero already
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const float yc = y[j] < 65504.0f ? y[j] : 65504.0f;  // saturate instead of overflowing to infinity
-                    hi[j] = (T)yc;
-                    lo[j] = (T)(yc - (float)hi[j]);
-                }
-                __builtin_nontemporal_store(*reinterpret_cast<f32x4*>(hi), reinterpret_cast<f32x4*>(out + off));
-                __builtin_nontemporal_store(*reinterpret_cast<f32x4*>(lo), reinterpret_cast<f32x4*>(out + off + 32));
-            }
+            finish_f16x2<CB, HAS_RES>(smem + stage_row<CB>(tile0, SP_ABUF, px), px, cg, ds8, bias8, resv[i], pslot0 + px < S * S, flags, sat,
+                                      out, wrow0 + px, cout, cout0 + cg * 8);
         }
     }
     STAMP(3);
@@ -1077,9 +1079,7 @@ __global__ void __launch_bounds__(512, 2)
     STAMP(0);
     STAMP_RT(5);
 
-    const int nblk = gridDim.x, ncb = cout / CPW;
-    int logical = blockIdx.x;
-    if ((nblk & 7) == 0) logical = (blockIdx.x & 7) * (nblk >> 3) + (blockIdx.x >> 3);
+    const int ncb = cout / CPW, logical = xcd_remap(blockIdx.x, gridDim.x);
     const int cout0 = (logical % ncb) * CPW;
     const int row0 = (logical / ncb) * RW;
 
@@ -1098,15 +1098,7 @@ __global__ void __launch_bounds__(512, 2)
         const int lw = wave - 4;
         uint32_t off_a[NHALF][SP_APL];
         int dst_a[NHALF][SP_APL];
-#pragma unroll
-        for (int g = 0; g < NHALF; g++)
-#pragma unroll
-            for (int i = 0; i < SP_APL; i++) {  // the padded image of a chunk, as in conv3x3_split_kernel
-                const int id = g * 18 + min(lw * SP_APL + i, 17);
-                const int sidx = id * 64 + lane, irow = sidx / 9, c = min(sidx - irow * 9, 7);
-                off_a[g][i] = (uint32_t)irow * row_bytes + c * 16;
-                dst_a[g][i] = id * 1024;
-            }
+        sp_image_pieces<NHALF>(off_a, dst_a, lw, lane, row_bytes);
         const char* abase0 = reinterpret_cast<const char*>(in) + (size_t)row0 * row_bytes;
         auto issue_chunk = [&](int ch) {  // activation chunk ch -> buffer ch & 1
             const char* src = abase0 + (size_t)ch * 128;
@@ -1117,28 +1109,11 @@ __global__ void __launch_bounds__(512, 2)
                 for (int i = 0; i < SP_APL; i++) glds16(src + off_a[g][i], dst + dst_a[g][i]);
         };
         if constexpr (STEM) {
-            // K0 fused (one chunk, no DMA): this thread expands pixel row (lw * 64 + lane) of the workgroup's RW rows
-            constexpr int MAXC = 32;
+            // K0 fused (one chunk, no DMA)
             const int row = lw * 64 + lane;
-            const uint32_t grow = (uint32_t)(row0 + row), slots = BIG ? 128u : 64u;
-            const uint32_t board = grow / slots, px = grow % slots;
-            const bool live = row < RW && board < sp.n && (int)px < S * S;
-            typedef const __attribute__((address_space(1))) uint64_t* gu64p;
-            const gu64p pl = (gu64p)(sp.planes + (size_t)(live ? board : 0) * sp.C * sp.w64 + (live ? (px >> 6) : 0));
-            uint64_t words[MAXC];
-#pragma unroll
-            for (int c = 0; c < MAXC; c++) words[c] = (live && (uint32_t)c < sp.C) ? pl[(size_t)c * sp.w64] : 0ull;
-            char* dstrow = smem + row * SP;
-#pragma unroll
-            for (int sl = 0; sl < 8; sl++) {
-                T vals[8];
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    const int c = sl * 8 + i;
-                    vals[i] = (c < MAXC && ((words[c < MAXC ? c : 0] >> (px & 63)) & 1ull)) ? (T)1.0f : (T)0.0f;
-                }
-                if (row < RW) *reinterpret_cast<f32x4*>(dstrow + sl * 16) = *reinterpret_cast<f32x4*>(vals);
-            }
+            uint64_t words[32];
+            const uint32_t px = stem_row_words<BIG>(words, sp, row0, row, row < RW, S);
+            stem_row_store<T>(smem + row * SP, 0, words, px, row < RW);
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // P
         } else {
             issue_chunk(0);
@@ -1158,21 +1133,9 @@ __global__ void __launch_bounds__(512, 2)
         }
         STAMP(1);
         for (int ch = 0; ch < nch; ch++) {
-            {
-                // chunk ch + 1 has landed (the younger skip rows may still be in flight at the first barrier)
-#ifdef CATTUS_STAMPS
-                const unsigned long long t0_ = __builtin_amdgcn_s_memtime();
-                if (HAS_RES && ch == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SKIP_PPW) : "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                const unsigned long long t1_ = __builtin_amdgcn_s_memtime();
-                asm volatile("s_barrier" ::: "memory");
-                st_[4] += t1_ - t0_;
-                st_[7] += __builtin_amdgcn_s_memtime() - t1_;
-#else
-                if (HAS_RES && ch == 0) wait_vm_barrier<SKIP_PPW>();
-                else wait_vm_barrier<0>();
-#endif
-            }
+            // chunk ch + 1 has landed (the younger skip rows may still be in flight at the first barrier)
+            if (HAS_RES && ch == 0) loader_wait_vm<SKIP_PPW>(st_);
+            else loader_wait_vm<0>(st_);
             if (ch + 2 < nch) issue_chunk(ch + 2);  // every consumer has read chunk ch: its buffer is free
         }
         STAMP(2);
@@ -1250,6 +1213,9 @@ __global__ void __launch_bounds__(512, 2)
     const int pslot0 = (wave % WPB) * PXW;           // this wave's first pixel slot of its board
     const int board_row = (wave / WPB) * SLOTS;      // first LDS row of this wave's board
     int rowa[9][PBW];
+    // sp_tap_rows, written out: with the call the compiler schedules this arithmetic (a division and some 150 VALU instructions)
+    // behind barrier P instead of in front of it, where it hides under the wait for chunk 0 -- on the 128-row tile that is 0.3 us of a
+    // 12 us launch (chess 20x256: 12.13 against 11.85 us at 17 leaves, 13.90 against 13.61 at 64)
 #pragma unroll
     for (int pb = 0; pb < PBW; pb++) {
         const int p = pslot0 + pb * 32 + r;
@@ -1271,9 +1237,6 @@ __global__ void __launch_bounds__(512, 2)
         for (int j = 0; j < PBW; j++)
 #pragma unroll
             for (int e = 0; e < 16; e++) acc[i][j][e] = 0.0f;
-
-    const size_t orow = (size_t)cout * 2;  // elements of T per row of `res` / `out`
-    const int ocol = ((cout0 + cg * 8) >> 5) * 64 + ((cout0 + cg * 8) & 31);  // hi values of the lane's 8 couts; lo 32 further
 
     {
         STAMP_ACC_BEGIN;
@@ -1336,8 +1299,8 @@ __global__ void __launch_bounds__(512, 2)
     for (int ch = 0; ch + 1 < nch; ch++) chunk(ch, std::false_type{});
     chunk(nch - 1, std::true_type{});
 
-    // ---- epilogue: as conv3x3_split_kernel (the last chunk's barrier has every wave out of the buffers); the skip values
-    // come from LDS ----
+    // ---- epilogue: stage_tile and finish_f16x2 as in conv3x3_split_kernel (the last chunk's barrier has every wave out of the
+    // buffers); the skip values come from LDS ----
     STAMP(2);
     {
         // all skip values of the lane at once (the ring's registers are free now): one LDS latency instead of one per trip
@@ -1352,73 +1315,12 @@ __global__ void __launch_bounds__(512, 2)
         }
         const size_t wrow0 = (size_t)row0 + wave * PXW;
         const int tile0 = wave * PXW * SP;  // the wave's own rows of buffer 0 (PXW x 144 B); the same rows of buffer 1 behind
-        auto stage_row = [&](int px) { return CB == 2 ? tile0 + (px >> 5) * ABUF + (px & 31) * 256 : tile0 + px * 128; };
-#pragma unroll
-        for (int cb = 0; cb < CB; cb++)
-#pragma unroll
-            for (int pb = 0; pb < PBW; pb++)
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    f32x4 v;
-#pragma unroll
-                    for (int i = 0; i < 4; i++) v[i] = acc[cb][pb][g * 4 + i];
-                    const int slot = (cb * 8 + g * 2 + h) ^ (r & 7);
-                    *reinterpret_cast<f32x4*>(smem + stage_row(pb * 32 + r) + slot * 16) = v;
-                }
+        stage_tile<CB, PBW>(acc, smem, tile0, ABUF, r, h);
 #pragma unroll
         for (int i = 0; i < EIT; i++) {
             const int px = i * RPT + prow;
-            const char* rowp = smem + stage_row(px);
-            const f32x4 lo4 = *reinterpret_cast<const f32x4*>(rowp + (((2 * cg) ^ (px & 7)) << 4));
-            const f32x4 hi4 = *reinterpret_cast<const f32x4*>(rowp + (((2 * cg + 1) ^ (px & 7)) << 4));
-            float v[8] = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-            // the inverse scale is a power of two, so the product is exact and one fused multiply-add rounds exactly as the
-            // multiply followed by the add of conv3x3_split_kernel does
-#pragma unroll
-            for (int j = 0; j < 8; j++) v[j] = __builtin_fmaf(v[j], ds8[j >> 2][j & 3], bias8[j >> 2][j & 3]);
-            if (HAS_RES) {
-#pragma unroll
-                for (int j = 0; j < 8; j++) v[j] = v[j] + ((float)resv[i][j] + (float)resv[i][8 + j]);  // hi + lo is exact in f32
-            }
-            const bool valid = pslot0 + px < S * S;  // slots past the board stay zero: masked once, on the packed vectors
-            float y[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) y[j] = v[j] > 0.0f ? v[j] : 0.0f;
-            const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-            if (flags & CONV_OUT_F32) {
-                if (flags & CONV_WINO_IN) cap_wino_input(y, valid, sat);
-                float* of = reinterpret_cast<float*>(out) + (wrow0 + px) * (size_t)cout + cout0 + cg * 8;
-                const f32x4 y0 = valid ? *reinterpret_cast<f32x4*>(y) : zero4, y1 = valid ? *reinterpret_cast<f32x4*>(y + 4) : zero4;
-                if constexpr (CB == 2) {
-                    __builtin_nontemporal_store(y0, reinterpret_cast<f32x4*>(of));
-                    __builtin_nontemporal_store(y1, reinterpret_cast<f32x4*>(of) + 1);
-                } else {  // small grid: the head kernels find the rows in L2 (see below)
-                    reinterpret_cast<f32x4*>(of)[0] = y0;
-                    reinterpret_cast<f32x4*>(of)[1] = y1;
-                }
-            } else {
-                const size_t off = (wrow0 + px) * orow + ocol;
-                T hi[8], lo[8];
-                note_saturation(y, valid, sat);
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const float yc = y[j] < 65504.0f ? y[j] : 65504.0f;
-                    hi[j] = (T)yc;
-                    lo[j] = (T)(yc - (float)hi[j]);
-                }
-                const f32x4 hi4o = valid ? *reinterpret_cast<f32x4*>(hi) : zero4, lo4o = valid ? *reinterpret_cast<f32x4*>(lo) : zero4;
-                if constexpr (CB == 2) {
-                    // the full grid: a layer's 16.7 MB of output and its 2.4 MB of weights do not fit the XCDs' L2 together
-                    __builtin_nontemporal_store(hi4o, reinterpret_cast<f32x4*>(out + off));
-                    __builtin_nontemporal_store(lo4o, reinterpret_cast<f32x4*>(out + off + 32));
-                } else {
-                    // the small-grid tile (<= 128 leaves of an 8x8 game): the output stays in the L2 of the XCD whose workgroups
-                    // read it back as the next layer's input (the block remap keeps a row block on one XCD): 18.5 us per
-                    // launch against 19.9 with non-temporal stores at batch 64, no difference at 128
-                    *reinterpret_cast<f32x4*>(out + off) = hi4o;
-                    *reinterpret_cast<f32x4*>(out + off + 32) = lo4o;
-                }
-            }
+            finish_f16x2<CB, HAS_RES>(smem + stage_row<CB>(tile0, ABUF, px), px, cg, ds8, bias8, resv[i], pslot0 + px < S * S, flags, sat,
+                                      out, wrow0 + px, cout, cout0 + cg * 8);
         }
     }
     STAMP(3);

@@ -135,22 +135,14 @@ __global__ void __launch_bounds__(256, 1) tower64_split_kernel(Tower64SplitArgs 
 
     // ---- per-lane constants ----
     const int r = lane & 31, h = lane >> 5;
-    int rowa[9][NPB];  // per tap and pixel block: byte offset of the shifted pixel's row in a chunk image (+ the lane half's 16 B)
+    // a wave's NPB pixel blocks lie in one board: workgroup rows pg * NPB * 32 on = pixel slots pslot0 on of the board at board_row
+    static_assert(NPB * 32 <= SLOTS && SLOTS % (NPB * 32) == 0, "a wave's pixel blocks must not straddle a board");
+    const int board_row = pg * NPB * 32 / SLOTS * SLOTS, pslot0 = pg * NPB * 32 % SLOTS;
+    int rowa[9][NPB];
+    sp_tap_rows<NPB>(rowa, board_row, pslot0, r, h, S, ZERO);
     bool pvalid[NPB];
 #pragma unroll
-    for (int pb = 0; pb < NPB; pb++) {
-        const int lrow = (pg * NPB + pb) * 32 + r;     // row of this lane's pixel inside the workgroup
-        const int board_row = lrow / SLOTS * SLOTS, p = lrow % SLOTS;
-        const int ph_ = p / S, pw = p - ph_ * S;
-        pvalid[pb] = p < hw;
-#pragma unroll
-        for (int t9 = 0; t9 < 9; t9++) {
-            const int hh = ph_ + t9 / 3 - 1, ww = pw + t9 % 3 - 1;
-            const bool ok = pvalid[pb] && (unsigned)hh < (unsigned)S && (unsigned)ww < (unsigned)S;
-            const int at = (board_row + hh * S + ww) * SP + h * 16;  // may lie outside the image when !ok: only its low 8 bits are used then
-            rowa[t9][pb] = ok ? at : ZERO + (at & 255);
-        }
-    }
+    for (int pb = 0; pb < NPB; pb++) pvalid[pb] = pslot0 + pb * 32 + r < hw;
     // epilogue addresses: this lane's accumulator element g * 4 + i is cout cb * 32 + g * 8 + h * 4 + i of pixel r: four
     // consecutive channels = 8 bytes of hi values at (g * 8 + h * 4) * 2 in the pixel's row of chunk cb, the lo values 64 further
     int erow[NPB];

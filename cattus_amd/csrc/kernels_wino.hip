@@ -81,9 +81,8 @@ __global__ void __launch_bounds__(256, 1)
     const int lane = tid & 63;
     const int r = lane & 31, h = lane >> 5;
 
-    const int nblk = gridDim.x, ncg = cout >> 7;
-    int logical = blockIdx.x;
-    if ((nblk & 7) == 0) logical = (blockIdx.x & 7) * (nblk >> 3) + (blockIdx.x >> 3);  // one XCD: all cout groups of a range of boards
+    const int ncg = cout >> 7;
+    const int logical = xcd_remap(blockIdx.x, gridDim.x);  // one XCD: all cout groups of a range of boards
     const int cout0 = (logical % ncg) * 128 + wave * 32;  // this wave's 32 output channels
     const int row0 = (logical / ncg) * WN_DROWS;          // first tower row of the workgroup's two boards
 

@@ -105,8 +105,7 @@ __device__ __forceinline__ void w4_layer(const float* __restrict__ in, const _Fl
     const int lane = tid & 63;
 
     const int ncg = cout >> 6;
-    int logical = wg;
-    if ((nblk & 7) == 0) logical = (wg & 7) * (nblk >> 3) + (wg >> 3);  // one XCD: all cout groups of a range of boards
+    const int logical = xcd_remap(wg, nblk);  // one XCD: all cout groups of a range of boards
     const int cout0 = (logical % ncg) * 64;   // the workgroup's 64 output channels
     const int row0 = (logical / ncg) * 256;   // first tower row of its four boards
 
