@@ -282,6 +282,10 @@ struct Lane {
     // page-locked word the error word is copied to behind every such launch
     DevBuf tower_layers, tower_ready;  // tower_ready: [error word, pad to 64 B | a counter per (layer, board group)] -- one memset per batch
     PinnedBuf h_tower_err;
+    // cattus_hip_verify, allocated when it is first turned on: a verified batch's [n records | n details] (kernels.h, launch_verify_outputs)
+    // on the device and in page-locked memory.  (The batch's planes are on the host either way: in the caller's page-locked buffer or in h_planes.)
+    DevBuf d_verify;
+    PinnedBuf h_verify;
     std::mutex mu;  // held while a batch uses the lane
     ~Lane() {
         if (done) (void)hipEventDestroy(done);
@@ -369,6 +373,22 @@ struct cattus_eval {
     cattus_stats stats{};
     uint64_t stats_tower_fallbacks = 0;  // batches the one-launch tower gave up on (run again on the per-layer launches)
 
+    // cattus_hip_verify: every verify_every-th batch of eval_host (0: none) also runs on `shadow`, a dtype f32 evaluator of the same blob that this
+    // one owns (built when verification is first turned on; its lane i is used under this evaluator's lane i mutex and by nobody else), and the two
+    // outputs are compared on the device.  verify_every and the shadow change only with every lane mutex held; eval_host reads them holding one
+    // (atomic for cattus_hip_verify_stats, which holds none).
+    uint64_t blob_hash = 0;  // of the blob this evaluator was created from, which it keeps no host copy of
+    size_t blob_bytes = 0;
+    std::atomic<uint32_t> verify_every{0};
+    std::atomic<uint64_t> verify_ticket{0};  // one per eval_host batch while verification is on: a batch is verified when ticket % verify_every == 0
+    cattus_eval* shadow = nullptr;
+    struct Verified {  // the sticky record, under stat_mu
+        uint64_t batches = 0, leaves = 0, leaves_outside = 0;
+        float max_dlogit = 0, logit = 0, logit_ref = 0, max_dvalue = 0, value = 0, value_ref = 0;
+        uint32_t move = 0;
+        std::vector<uint64_t> worst_planes;  // of the leaf that holds max_dlogit; empty before any leaf was verified
+    } verified;
+
     // leaf server
     std::mutex srv_mu;
     std::condition_variable srv_cv, done_cv;
@@ -386,6 +406,7 @@ struct cattus_eval {
         done_cv.notify_all();
         for (auto& t : servers)
             if (t.joinable()) t.join();
+        delete shadow;
     }
 };
 
@@ -402,6 +423,19 @@ size_t blob_floats(const cattus_net_desc& d) {
     n += (size_t)d.vhc * F + 2 * (size_t)d.vhc + (size_t)FC_HIDDEN * d.vhc * hw + FC_HIDDEN + FC_HIDDEN + 1;
     n += (size_t)d.phc * F + 2 * (size_t)d.phc + (size_t)d.moves * d.phc * hw + d.moves;
     return n;
+}
+
+// 64 bits of the blob, FNV-1a taken over 8-byte words (a trailing partial word zero-padded): how cattus_hip_verify knows the blob it is handed
+// for the one the evaluator was created from.  ~10 ms for chess 20x256's 95 MB, once per create.
+uint64_t blob_hash64(const void* p, size_t nbytes) {
+    uint64_t h = 0xcbf29ce484222325ull ^ nbytes;
+    const char* c = static_cast<const char*>(p);
+    for (size_t at = 0; at < nbytes; at += 8) {
+        uint64_t w = 0;
+        memcpy(&w, c + at, std::min<size_t>(8, nbytes - at));
+        h = (h ^ w) * 0x100000001b3ull;
+    }
+    return h;
 }
 
 // Launches of the persistent tower never overlap on a device: each waits for the one before it (an event chain per device, process-wide:
@@ -814,14 +848,16 @@ int enqueue_forward(cattus_eval* e, Lane& L, const uint64_t* d_planes, uint32_t 
     return CATTUS_OK;
 }
 
-// seconds: of a batch whose wait was measured; nullptr: the counters alone (an asynchronous entry point measures no time)
-void account(cattus_eval* e, uint32_t n, const double* seconds) {
+// seconds: of a batch whose wait was measured; nullptr: the counters alone (an asynchronous entry point measures no time).  verified: the batch
+// also ran on the shadow tower (cattus_hip_verify) -- the caller did wait for that, so the total has it, but the average is the reference's
+// model.run_duration, whose 0.99 weight makes it the last batch: a batch several times as long as its neighbours stays out of it.
+void account(cattus_eval* e, uint32_t n, const double* seconds, bool verified = false) {
     std::lock_guard<std::mutex> lk(e->stat_mu);
     cattus_stats& s = e->stats;
     if (seconds) {
         // RunningAverage::set with epsilon 0.99, starting from 0 (reference: engine/src/util/metric.rs:1-20,
         // engine/src/net/mod.rs:36): value = (1 - eps) * value + eps * new
-        s.run_seconds_ema = 0.01 * s.run_seconds_ema + 0.99 * *seconds;
+        if (!verified) s.run_seconds_ema = 0.01 * s.run_seconds_ema + 0.99 * *seconds;
         s.run_seconds_total += *seconds;
     }
     s.batches += 1;
@@ -861,6 +897,27 @@ Lane& take_lane(cattus_eval* e, std::unique_lock<std::mutex>& lk) {
     return lane;
 }
 
+// A verified batch's n records, then its n details (kernels.h, launch_verify_outputs), into the sticky record, in leaf order.  The first
+// verified leaf seeds the worst-logit entry, so that there are planes to ask for from then on; after that only a strictly larger difference
+// replaces an entry: the first occurrence of a maximum stays.  A NaN |dvalue| (a non-finite value: its leaf is counted outside) replaces nothing.
+void fold_verified(cattus_eval* e, const VerifyRecord* rec, uint32_t n, const uint64_t* planes) {
+    const size_t words = (size_t)e->d.planes * e->cfg.plane_words;
+    const float* detail = reinterpret_cast<const float*>(rec + n);
+    std::lock_guard<std::mutex> lk(e->stat_mu);
+    cattus_eval::Verified& v = e->verified;
+    v.batches += 1;
+    for (uint32_t i = 0; i < n; i++) {
+        const float* dt = detail + (size_t)i * 4;
+        v.leaves_outside += rec[i].flags & VERIFY_LEAF_OUTSIDE;
+        if (v.worst_planes.empty() || rec[i].max_dlogit > v.max_dlogit) {
+            v.max_dlogit = rec[i].max_dlogit, v.move = rec[i].move, v.logit = dt[0], v.logit_ref = dt[1];
+            v.worst_planes.assign(planes + i * words, planes + (i + 1) * words);
+        }
+        if (rec[i].dvalue > v.max_dvalue) v.max_dvalue = rec[i].dvalue, v.value = dt[2], v.value_ref = dt[3];
+    }
+    v.leaves += n;
+}
+
 // Blocking host-buffer evaluation; caller holds no lock.  With `lg` the logits stay on the device and
 // the per-leaf softmax over the legal moves comes back instead (policy is not written).
 int eval_host(cattus_eval* e, const uint64_t* planes, uint32_t n, float* policy, float* value, const LegalArgs* lg = nullptr) {
@@ -870,6 +927,9 @@ int eval_host(cattus_eval* e, const uint64_t* planes, uint32_t n, float* policy,
     const RoctxRange range(lg ? "cattus_hip_eval_legal" : "cattus_hip_eval", n);
     HIP_TRY(hipSetDevice(e->device));
     const auto t0 = std::chrono::steady_clock::now();
+    // cattus_hip_verify: while it is on every batch takes a ticket, and every verify_every-th one -- the first one first -- is checked
+    const uint32_t every = e->verify_every.load(std::memory_order_relaxed);
+    const bool verify = every && e->verify_ticket.fetch_add(1, std::memory_order_relaxed) % every == 0;
     const size_t pbytes = (size_t)n * d.planes * e->cfg.plane_words * 8;
     // Buffers obtained from cattus_hip_host_alloc are page-locked: DMA straight from / into them.
     // Anything else goes through the evaluator's own pinned staging buffers.
@@ -908,6 +968,17 @@ int eval_host(cattus_eval* e, const uint64_t* planes, uint32_t n, float* policy,
     auto run_batch = [&]() -> int {
         int rc = enqueue_forward(e, L, L.d_planes.as<uint64_t>(), n, L.d_policy.as<float>(), L.d_value.as<float>(), L.stream);
         if (rc) return rc;
+        if (verify) {
+            // the same device-resident leaves through the shadow's lane of this index, on this lane's stream, behind the evaluator's own pass:
+            // it writes the shadow lane's buffers only, so what the copies below return is what they return without it.  (A batch the one-launch
+            // tower gives up on comes through here twice; its second run's records are the ones that are folded.)
+            Lane& SL = e->shadow->lanes[&L - e->lanes];
+            if ((rc = enqueue_forward(e->shadow, SL, L.d_planes.as<uint64_t>(), n, SL.d_policy.as<float>(), SL.d_value.as<float>(), L.stream))) return rc;
+            VerifyRecord* const rec = L.d_verify.as<VerifyRecord>();
+            launch_verify_outputs(L.d_policy.as<float>(), SL.d_policy.as<float>(), L.d_value.as<float>(), SL.d_value.as<float>(), n, d.moves, rec,
+                                  reinterpret_cast<float*>(rec + n), L.stream);
+            HIP_TRY(hipMemcpyAsync(L.h_verify.p, rec, (size_t)n * 2 * sizeof(VerifyRecord), hipMemcpyDeviceToHost, L.stream));
+        }
         if ((rc = copy_out())) return rc;
         if (e->wait_spin) {
             HIP_TRY(hipStreamSynchronize(L.stream));
@@ -924,8 +995,9 @@ int eval_host(cattus_eval* e, const uint64_t* planes, uint32_t n, float* policy,
         if (!lg) memcpy(policy, L.h_policy.p, (size_t)n * d.moves * 4);
         memcpy(value, L.h_value.p, (size_t)n * 4);
     }
+    if (verify) fold_verified(e, L.h_verify.as<VerifyRecord>(), n, static_cast<const uint64_t*>(src_planes));
     const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    account(e, n, &seconds);
+    account(e, n, &seconds, verify);
     return CATTUS_OK;
 }
 
@@ -1155,6 +1227,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
     std::unique_ptr<cattus_eval> e(new (std::nothrow) cattus_eval);
     if (!e) return fail(CATTUS_E_NOMEM, "out of memory");
     e->d = d, e->cfg = *cfg;
+    e->blob_hash = blob_hash64(weights, nbytes), e->blob_bytes = nbytes;
     if (e->cfg.flush_us == 0) e->cfg.flush_us = 200;
     e->device = cfg->device;
     e->wait_spin = !(wait_mode && strcmp(wait_mode, "block") == 0);
@@ -1472,6 +1545,77 @@ CATTUS_API int cattus_hip_stats(cattus_eval* e, cattus_stats* out) {
     std::lock_guard<std::mutex> lk(e->stat_mu);
     e->stats.saturated = sat;
     *out = e->stats;
+    return CATTUS_OK;
+}
+
+CATTUS_API int cattus_hip_verify(cattus_eval* e, const void* weights, size_t nbytes, uint32_t every) {
+    if (!e || !weights) return fail(CATTUS_E_INVALID, "NULL argument");
+    if (e->plan.kind == TowerKind::Simple) return fail(CATTUS_E_UNSUPPORTED, "a SimpleTwoHeadedModel runs in f32 whatever its dtype: there is nothing to verify it against");
+    if (e->act == Act::F32) return fail(CATTUS_E_UNSUPPORTED, "a dtype f32 evaluator is the exact tower: its shadow would be itself");
+    if (nbytes != e->blob_bytes || blob_hash64(weights, nbytes) != e->blob_hash)
+        return fail(CATTUS_E_INVALID, "verify: this is not the weight blob the evaluator was created from");
+    std::unique_lock<std::mutex> held[NLANES];  // every lane, in lane order: batches in flight finish first, none starts meanwhile
+    for (int i = 0; i < NLANES; i++) held[i] = std::unique_lock<std::mutex>(e->lanes[i].mu);
+    if (every && !e->shadow) {
+        HIP_TRY(hipSetDevice(e->device));
+        // the same blob on the same device with the same max_batch and plane_words, dtype f32, no switches
+        cattus_eval_config scfg = e->cfg;
+        scfg.dtype = CATTUS_DTYPE_F32, scfg.tower_form = CATTUS_TOWER_AUTO;
+        cattus_eval* shadow = nullptr;
+        if (int rc = create_impl(weights, nbytes, &scfg, nullptr, &shadow)) return rc;  // CATTUS_E_NOMEM where it does not fit
+        const size_t bytes = (size_t)e->cfg.max_batch * 2 * sizeof(VerifyRecord);
+        for (Lane& L : e->lanes) {
+            int rc = CATTUS_OK;
+            if (!L.d_verify.p) rc = L.d_verify.alloc(bytes);
+            if (!rc && !L.h_verify.p) rc = L.h_verify.alloc(bytes);
+            if (rc) {
+                delete shadow;
+                return rc;
+            }
+        }
+        e->shadow = shadow;
+    }
+    e->verify_every = every;  // 0: off -- the record and the shadow stay, and turning it on again goes on counting
+    return CATTUS_OK;
+}
+
+CATTUS_API int cattus_hip_verify_stats(cattus_eval* e, cattus_verify_stats* out) {
+    if (!e || !out) return fail(CATTUS_E_INVALID, "NULL argument");
+    if (out->struct_size != sizeof(cattus_verify_stats)) return fail(CATTUS_E_INVALID, "cattus_verify_stats.struct_size mismatch");
+    const uint32_t every = e->verify_every.load(std::memory_order_relaxed);
+    std::lock_guard<std::mutex> lk(e->stat_mu);
+    const cattus_eval::Verified& v = e->verified;
+    *out = cattus_verify_stats{(uint32_t)sizeof(cattus_verify_stats), every, v.batches, v.leaves, v.leaves_outside, v.max_dlogit, v.logit, v.logit_ref, v.move,
+                               v.max_dvalue, v.value, v.value_ref, 0};
+    return CATTUS_OK;
+}
+
+CATTUS_API int cattus_hip_verify_worst_planes(cattus_eval* e, uint64_t* planes) {
+    if (!e || !planes) return fail(CATTUS_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(e->stat_mu);
+    if (e->verified.worst_planes.empty()) return fail(CATTUS_E_STATE, "no leaf has been verified yet");
+    std::copy(e->verified.worst_planes.begin(), e->verified.worst_planes.end(), planes);
+    return CATTUS_OK;
+}
+
+CATTUS_API int cattus_hip_compare_outputs(int device, const float* policy_a, const float* policy_b, const float* value_a, const float* value_b, uint32_t n,
+                                          uint32_t moves, void* records) {
+    if (!policy_a || !policy_b || !value_a || !value_b || !records) return fail(CATTUS_E_INVALID, "NULL argument");
+    if (n < 1 || moves < 1 || (uint64_t)n * moves > (1ull << 30)) return fail(CATTUS_E_INVALID, "compare_outputs: %u leaves of %u moves", n, moves);
+    int ndev = 0;
+    hipError_t herr = hipGetDeviceCount(&ndev);
+    if (herr != hipSuccess || device < 0 || device >= ndev)
+        return fail(CATTUS_E_DEVICE, "no usable HIP device %d (%s); this library has no CPU path", device, hipGetErrorString(herr));
+    HIP_TRY(hipSetDevice(device));
+    DevBuf pa, pb, va, vb, rec;
+    int rc;
+    const size_t pbytes = (size_t)n * moves * 4;
+    if ((rc = pa.upload(policy_a, pbytes)) || (rc = pb.upload(policy_b, pbytes)) || (rc = va.upload(value_a, (size_t)n * 4)) || (rc = vb.upload(value_b, (size_t)n * 4)) ||
+        (rc = rec.alloc((size_t)n * sizeof(VerifyRecord))))
+        return rc;
+    launch_verify_outputs(pa.as<float>(), pb.as<float>(), va.as<float>(), vb.as<float>(), n, moves, rec.as<VerifyRecord>(), nullptr, nullptr);
+    if (hipError_t err = hipGetLastError()) return fail(CATTUS_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(err));
+    HIP_TRY(hipMemcpy(records, rec.p, (size_t)n * sizeof(VerifyRecord), hipMemcpyDeviceToHost));
     return CATTUS_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "frag_index.h"  // split_frag_index, wino_frag_index, WINO_RING_STAGES
+#include "verify_rule.h"  // VerifyRecord and the rule behind it
 
 namespace cattus {
 
@@ -122,6 +123,13 @@ void launch_tower_wino4(const Wino4TowerLayer* d_layers, uint32_t nlayers, unsig
 size_t stream_range_parts(uint32_t bpad, uint32_t S);
 void launch_stream_range(const float* rows, uint32_t nb, uint32_t n, uint32_t S, uint32_t FP, double* part_sq, float* part_max, double* acc_sq,
                          float* acc_max, hipStream_t st);
+
+// ---- verification: an evaluator's outputs against its f32 shadow's (cattus_hip_verify, cattus_hip_compare_outputs) ----
+// policy_a / policy_b: [n][M] logits, value_a / value_b: [n], b the shadow's; records: [n], 16-byte aligned, one verify_rule.h verdict per
+// leaf; detail: NULL, or [n][4] floats, 16-byte aligned: logit_a, logit_b at the record's move, value_a, value_b.  The same inputs give the
+// same bytes on every run (no atomics).
+void launch_verify_outputs(const float* policy_a, const float* policy_b, const float* value_a, const float* value_b, uint32_t n, uint32_t M,
+                           VerifyRecord* records, float* detail, hipStream_t st);
 
 // Diagnostic: one launch of nothing but back-to-back MFMAs of the tower's kind (F16S: f16, BF16, F32: 32x32x2 f32), four
 // waves on each of `cus` workgroups, iters x 4 MFMAs per wave; `out` holds cus * 256 floats.  Returns the launch's FLOPs.

@@ -14,6 +14,8 @@
 //       head_conv1x1, value_fc1, value_fc2_tanh, policy_fc   the same on the generic path (SIMT f32)
 //       stream_range, stream_range_finish                   calibration: per-channel sum of squares and maximum of an f32 stream tensor
 //                                                           (HBM-trivial, once per calibrated evaluator, never per batch)
+//       verify_outputs                                      verification: two runtimes' logits and values of a batch against the reference's
+//                                                           cross-runtime bar, one record per leaf (HBM-trivial, verified batches only)
 //
 // Arithmetic the kernels reproduce: ConvNetV1.forward in eval mode
 // (reference: training/cattus_train/net_utils.py:4-89) on the tensor planes_to_tensor builds
@@ -2517,6 +2519,62 @@ void launch_stream_range(const float* rows, uint32_t nb, uint32_t n, uint32_t S,
     }
     hipLaunchKernelGGL(stream_range_kernel, dim3(parts, FP / 64), dim3(256), 0, st, rows, n, slots, S * S, FP, part_sq, part_max);
     hipLaunchKernelGGL(stream_range_finish_kernel, dim3(FP / 64), dim3(64), 0, st, part_sq, part_max, parts, FP, acc_sq, acc_max);
+}
+
+// ------------------------------------------------------------------------------------------
+// Verification: an evaluator's outputs against its f32 shadow's (cattus_hip_verify, cattus_hip_compare_outputs)
+// ------------------------------------------------------------------------------------------
+// One wave per leaf, four leaves per workgroup; verify_rule.h is the rule.  A leaf's two logit rows [M] are read as 16-byte vectors from
+// the first 16-byte boundary on -- a wave's 64 vectors are 1 KiB contiguous, whole 128-byte lines -- with the up to three floats in front
+// of it and behind the last whole vector read one by one (chess rows, M = 1880, start on a boundary; M = 67 or 9 rows do not).  Two rows
+// that sit differently against the boundary (never the evaluator's own buffers) are read float by float throughout.  Each lane keeps the
+// running maximum of its moves, a butterfly of shuffles folds the 64 -- verify_take_max gives the same pair in any order, so the record
+// is the same bytes on every run; no atomics -- and lane 0 writes the record with one 16-byte store.  detail (may be NULL): per leaf
+// [logit_a, logit_b at the record's move | value_a, value_b], what the evaluator's sticky record keeps of the worst leaf.
+__global__ void __launch_bounds__(256) verify_outputs_kernel(const float* __restrict__ policy_a, const float* __restrict__ policy_b,
+                                                             const float* __restrict__ value_a, const float* __restrict__ value_b, uint32_t n, uint32_t M,
+                                                             VerifyRecord* __restrict__ records, f32x4* __restrict__ detail) {
+    const uint32_t lane = threadIdx.x & 63, leaf = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (leaf >= n) return;  // whole waves leave: nothing below synchronises across waves
+    const float* ra = policy_a + (size_t)leaf * M;
+    const float* rb = policy_b + (size_t)leaf * M;
+    const uint32_t mis_a = (uint32_t)(reinterpret_cast<uintptr_t>(ra) & 15), mis_b = (uint32_t)(reinterpret_cast<uintptr_t>(rb) & 15);
+    uint32_t head = mis_a == mis_b ? ((16 - mis_a) & 15) / 4 : M;  // floats in front of the first common 16-byte boundary
+    head = head < M ? head : M;
+    const uint32_t nvec = (M - head) / 4, tail = head + nvec * 4;
+    float best_d = 0.0f;
+    uint32_t best_i = 0xffffffffu;
+    bool outside = false;
+    auto take = [&](float a, float b, uint32_t i) {
+        verify_take_max(verify_dlogit(a, b), i, best_d, best_i);
+        outside = outside || !verify_logit_inside(a, b);
+    };
+    for (uint32_t i = lane; i < head; i += 64) take(ra[i], rb[i], i);
+    for (uint32_t v = lane; v < nvec; v += 64) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(ra + head + v * 4), b = *reinterpret_cast<const f32x4*>(rb + head + v * 4);
+#pragma unroll
+        for (int j = 0; j < 4; j++) take(a[j], b[j], head + v * 4 + j);
+    }
+    for (uint32_t i = tail + lane; i < M; i += 64) take(ra[i], rb[i], i);
+    for (int off = 32; off; off >>= 1) {
+        const float od = __shfl_xor(best_d, off);
+        const uint32_t oi = (uint32_t)__shfl_xor((int)best_i, off);
+        verify_take_max(od, oi, best_d, best_i);
+    }
+    outside = __any(outside);
+    if (lane == 0) {
+        const float va = value_a[leaf], vb = value_b[leaf];
+        const VerifyRecord r = verify_record(best_d, best_i, outside, va, vb);
+        *reinterpret_cast<uint4*>(records + leaf) = make_uint4(__float_as_uint(r.max_dlogit), r.move, __float_as_uint(r.dvalue), r.flags);
+        if (detail) detail[leaf] = f32x4{ra[r.move], rb[r.move], va, vb};
+    }
+}
+
+void launch_verify_outputs(const float* policy_a, const float* policy_b, const float* value_a, const float* value_b, uint32_t n, uint32_t M,
+                           VerifyRecord* records, float* detail, hipStream_t st) {
+    if (!n) return;
+    hipLaunchKernelGGL(verify_outputs_kernel, dim3((n + 3) / 4), dim3(256), 0, st, policy_a, policy_b, value_a, value_b, n, M, records,
+                       reinterpret_cast<f32x4*>(detail));
 }
 
 // ------------------------------------------------------------------------------------------

@@ -53,6 +53,10 @@ ABI_SYMBOLS = [
     "cattus_hip_tower_kernel",
     "cattus_hip_stream_range",
     "cattus_hip_create_calibrated",
+    "cattus_hip_verify",
+    "cattus_hip_verify_stats",
+    "cattus_hip_verify_worst_planes",
+    "cattus_hip_compare_outputs",  # include/cattus_hip_diag.h
     "cattus_hip_create_diag",  # include/cattus_hip_diag.h
     "cattus_hip_create_calibrated_diag",  # include/cattus_hip_diag.h
     "cattus_hip_stream_shift",  # include/cattus_hip_diag.h
@@ -101,6 +105,29 @@ class Stats(C.Structure):
 
 class ChannelRange(C.Structure):
     _fields_ = [("rms", C.c_float), ("abs_max", C.c_float)]
+
+
+class VerifyStats(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("every", C.c_uint32),
+        ("batches", C.c_uint64),
+        ("leaves", C.c_uint64),
+        ("leaves_outside", C.c_uint64),
+        ("max_dlogit", C.c_float),
+        ("logit", C.c_float),
+        ("logit_ref", C.c_float),
+        ("move", C.c_uint32),
+        ("max_dvalue", C.c_float),
+        ("value", C.c_float),
+        ("value_ref", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+
+# one leaf's verdict of the comparison kernel (include/cattus_hip_diag.h, cattus_hip_compare_outputs): flags bit 0 the leaf is
+# outside the bar, bit 1 its value is
+VERIFY_RECORD = np.dtype([("max_dlogit", "<f4"), ("move", "<u4"), ("dvalue", "<f4"), ("flags", "<u4")])
 
 
 class NetDescC(C.Structure):
@@ -158,6 +185,10 @@ def load_library():
     L.cattus_hip_stream_shift.argtypes = [vp]
     L.cattus_hip_stream_shifts.argtypes = [vp, C.POINTER(C.c_int), C.c_uint32]
     L.cattus_hip_stem_input.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.cattus_hip_verify.argtypes = [vp, vp, C.c_size_t, C.c_uint32]
+    L.cattus_hip_verify_stats.argtypes = [vp, C.POINTER(VerifyStats)]
+    L.cattus_hip_verify_worst_planes.argtypes = [vp, u64p]
+    L.cattus_hip_compare_outputs.argtypes = [C.c_int, f32p, f32p, f32p, f32p, C.c_uint32, C.c_uint32, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("cattus_hip_last_error", "cattus_hip_version", "cattus_hip_runtime_note", "cattus_hip_host_alloc",
@@ -192,6 +223,18 @@ def planes_to_tensor(planes: np.ndarray, board: int, batch_size: int, device: in
     return out
 
 
+def compare_outputs(policy_a, policy_b, value_a, value_b, device: int = 0) -> np.ndarray:
+    """The comparison kernel of ``HipEvaluator.verify`` on host arrays (cattus_hip_compare_outputs, include/cattus_hip_diag.h):
+    float32 ``[n, M]`` logits and ``[n]`` values of two runtimes, b the reference side -> ``[n]`` records of dtype VERIFY_RECORD."""
+    pa, pb = (np.ascontiguousarray(p, dtype=np.float32) for p in (policy_a, policy_b))
+    va, vb = (np.ascontiguousarray(v, dtype=np.float32) for v in (value_a, value_b))
+    if pa.ndim != 2 or pa.shape != pb.shape or va.shape != (pa.shape[0],) or vb.shape != va.shape:
+        raise ValueError("compare_outputs: policies [n, M] and values [n] of both sides")
+    out = np.zeros(pa.shape[0], dtype=VERIFY_RECORD)
+    _check(load_library().cattus_hip_compare_outputs(device, _f32(pa), _f32(pb), _f32(va), _f32(vb), pa.shape[0], pa.shape[1], out.ctypes.data))
+    return out
+
+
 class HipEvaluator:
     """One network resident on one MI355X.
 
@@ -211,12 +254,14 @@ class HipEvaluator:
         tower_form: str | None = None,
         switches: dict | None = None,
         calibration=None,
+        verify_every: int = 0,
     ):
         """tower_form: "auto" | "direct" | "winograd" (cattus_tower_form; None = "auto", or what CATTUS_WINOGRAD=0/1 in the
         environment says).  switches: diagnostic switches for cattus_hip_create_diag (None = the CATTUS_* ones found in the
         environment, {} = none).  calibration: sample positions, uint64 ``[n, C, plane_words]`` -- the f16 / f16x2 towers then
         take their stream shifts from the range measured on them instead of from the BatchNorm parameters
-        (cattus_hip_create_calibrated; nothing to calibrate for f32 / bf16, which come out as without it)."""
+        (cattus_hip_create_calibrated; nothing to calibrate for f32 / bf16, which come out as without it).  verify_every: N >= 1
+        checks every Nth batch against a shadow f32 tower (``verify``); 0, the default, builds no shadow and checks nothing."""
         self.desc: NetDesc = parse_header(blob)
         self.batch_size = int(batch_size)
         self.plane_words = int(plane_words)
@@ -246,6 +291,13 @@ class HipEvaluator:
         else:
             _check(self._lib.cattus_hip_create(buf, len(blob), C.byref(cfg), C.byref(h)))
         self._h = h
+        self._blob = blob  # cattus_hip_verify takes it again: the library keeps no host copy
+        if verify_every:
+            try:
+                self.verify(verify_every)
+            except Exception:
+                self.close()
+                raise
 
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):
@@ -337,6 +389,28 @@ class HipEvaluator:
         s = Stats()
         _check(self._lib.cattus_hip_stats(self._h, C.byref(s)))
         return {name: getattr(s, name) for name, _ in Stats._fields_}
+
+    # -- verification against a shadow f32 tower (include/cattus_hip.h, cattus_hip_verify) ----
+    def verify(self, every: int, blob: bytes | None = None):
+        """Check every ``every``-th batch of eval / eval_legal / the leaf server against an f32 evaluator of the same blob, built
+        here on first use (a second copy of the weights in f32; a verified batch costs an f32 pass on top of its own); 0 turns it
+        off and keeps the record.  The outputs returned are the evaluator's own either way.  blob: the evaluator's own unless
+        given (the library refuses any other)."""
+        blob = self._blob if blob is None else blob
+        _check(self._lib.cattus_hip_verify(self._h, blob, len(blob), int(every)))
+
+    def verify_stats(self) -> dict:
+        """The sticky record: every, batches, leaves, leaves_outside (of the reference's cross-runtime bar: > 0 means what
+        saturated > 0 means), max_dlogit with its move and both logits (logit_ref the f32 one), max_dvalue with both values."""
+        s = VerifyStats(struct_size=C.sizeof(VerifyStats))
+        _check(self._lib.cattus_hip_verify_stats(self._h, C.byref(s)))
+        return {name: getattr(s, name) for name, _ in VerifyStats._fields_ if name not in ("struct_size", "reserved")}
+
+    def verify_worst_planes(self) -> np.ndarray:
+        """uint64 ``[C, plane_words]``: the leaf that holds max_dlogit (raises with status CATTUS_E_STATE before any was verified)."""
+        out = np.zeros((self.desc.planes, self.plane_words), dtype=np.uint64)
+        _check(self._lib.cattus_hip_verify_worst_planes(self._h, _u64(out)))
+        return out
 
     def tower_kernel(self) -> str:
         """Name of the kernel that runs this evaluator's tower."""

@@ -542,6 +542,10 @@ def write_summary(path, summary: dict):
             "model.saturated": summary.get("saturated", 0),
         },
     }
+    # model.inference.verify_every: what the shadow f32 tower found (HipEvaluator.verify_stats), summed over the models that played
+    for key in ("verified_leaves", "leaves_outside_bar", "max_dlogit", "max_dvalue"):
+        if key in summary:
+            out["metrics"]["model." + key] = summary[key]
     with open(path, "x") as f:  # create_new, as the reference
         json.dump(out, f)
 
@@ -569,11 +573,13 @@ def main(argv=None):
         raise SystemExit(f"this self-player only implements the 'hip' inference engine, got {inf.get('engine')!r}")
     info = game_info(args.game)
     cfg = config_from_engine_json(engine, concurrent_games=engine.get("concurrent_games", 0))
+    # optional: check every Nth batch against a shadow f32 tower (include/cattus_hip.h, cattus_hip_verify); absent or 0: no check
+    verify_every = int(inf.get("verify_every", 0))
 
     def load(path):
         blob = Path(path).read_bytes()
         return HipEvaluator(blob, batch_size=engine["model"]["batch_size"], plane_words=info["plane_words"],
-                            dtype=inf.get("dtype", "f16x2"), device=inf.get("device", 0))
+                            dtype=inf.get("dtype", "f16x2"), device=inf.get("device", 0), verify_every=verify_every)
 
     ev1 = load(args.model1_path)
     same = os.path.abspath(args.model1_path) == os.path.abspath(args.model2_path)
@@ -587,6 +593,18 @@ def main(argv=None):
 
         print(f"{Path(sys.argv[0]).name}: WARNING: {res['saturated']} activation values left the f16 range and were clamped: the "
               f"outputs of dtype {inf.get('dtype', 'f16x2')!r} are not this network's -- use \"dtype\": \"f32\" in model.inference", file=sys.stderr)
+    if verify_every:
+        vs = [ev.verify_stats() for ev in (ev1, ev2) if ev is not None]
+        res["verified_leaves"] = sum(v["leaves"] for v in vs)
+        res["leaves_outside_bar"] = sum(v["leaves_outside"] for v in vs)
+        res["max_dlogit"] = max(v["max_dlogit"] for v in vs)  # the largest seen by either model: a maximum does not sum
+        res["max_dvalue"] = max(v["max_dvalue"] for v in vs)
+        if res["leaves_outside_bar"]:
+            import sys
+
+            print(f"{Path(sys.argv[0]).name}: WARNING: {res['leaves_outside_bar']} of {res['verified_leaves']} verified leaves are outside the "
+                  f"reference's cross-runtime tolerance of the f32 tower (max |dlogit| {res['max_dlogit']:.3g}, max |dvalue| {res['max_dvalue']:.3g}): "
+                  f"use \"dtype\": \"f32\" in model.inference, or calibrate", file=sys.stderr)
     if args.summary_file:
         write_summary(args.summary_file, res)
 

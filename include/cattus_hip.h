@@ -183,6 +183,48 @@ void cattus_hip_host_free(void* p);
 
 int cattus_hip_stats(cattus_eval* e, cattus_stats* out);
 
+/* Live verification against a shadow f32 tower.  `saturated` above fires only when the f16 range is left; this tells how far a bf16 /
+ * f16 / f16x2 evaluator is from the exact network on the positions it is actually given.  With every >= 1, every `every`-th batch of
+ * the blocking entry points (cattus_hip_eval, cattus_hip_eval_legal, and the leaf server behind submit / wait / apply) is, behind its
+ * own forward pass and on the same device-resident leaves, also run through a dtype f32 evaluator of the same blob that this evaluator
+ * builds on first use and owns; the two outputs are compared on the device, and a small sticky record is kept.  Batches take a ticket
+ * each while verification is on, counted from 0, and ticket % every == 0 is verified: with verification on from the start an
+ * evaluator's first batch is always checked.  every == 0 turns it off again: the record and the shadow stay, and turning it on once
+ * more goes on counting.  What the caller gets back for a verified batch is bit for bit what it gets without verification;
+ * cattus_stats counts what it counted before (the shadow pass is no batch), except that run_seconds_ema leaves verified batches out
+ * (run_seconds_total has them: the caller did wait).  The asynchronous device entry points, cattus_hip_eval_device and
+ * cattus_hip_eval_device_lane, do NOT verify.
+ *
+ * The bar is the reference's own cross-runtime tolerance (training/tests/test_net_output.py:28-33), with the f32 shadow as the
+ * reference side: a logit is inside when |a - b| <= 1e-6 + 1e-3 |b|, a value when |a - b| <= max(1e-5 max(|a|, |b|), 1e-6), both in
+ * double; a non-finite operand is outside; two scrubbed logits (both f32::MIN) differ by 0 and are inside.  A leaf is outside when its
+ * value or any of its logits is.
+ *
+ * Cost.  The shadow is a second copy of the weights, in f32, plus two lanes of f32 activations in HBM (CATTUS_E_NOMEM where that does
+ * not fit).  A verified batch costs one f32 tower pass on top of its own -- several times its own length -- and the f32 pass
+ * displaces the Winograd tower's working set in the Infinity Cache, which the batch behind it pays for;
+ * profiles/verify_cost.txt has what every = 1, 8 and 64 were measured to cost on chess 20x256.
+ *
+ * leaves_outside > 0 means what saturated > 0 means: outputs of this evaluator are not the network's by the reference's own bar -- use
+ * dtype f32 for that network, or calibrate (cattus_hip_create_calibrated).
+ *
+ * `weights` is the blob the evaluator was created from, passed again because the evaluator keeps no host copy of it: another blob
+ * (by size or by a 64-bit hash taken at create) is CATTUS_E_INVALID.  A dtype f32 evaluator (the shadow would be itself) and a
+ * SimpleTwoHeadedModel (f32 whatever the dtype) are CATTUS_E_UNSUPPORTED.  The call waits for the batches in flight. */
+typedef struct cattus_verify_stats {
+    uint32_t struct_size;   /* in: sizeof(cattus_verify_stats) */
+    uint32_t every;         /* 0 = off */
+    uint64_t batches, leaves, leaves_outside;
+    float max_dlogit, logit, logit_ref; uint32_t move;   /* the largest |dlogit| seen and where: this evaluator's logit, the shadow's, the move index */
+    float max_dvalue, value, value_ref; uint32_t reserved;
+} cattus_verify_stats;
+int cattus_hip_verify(cattus_eval* e, const void* weights, size_t nbytes, uint32_t every);
+/* The sticky record since the evaluator was created.  Of several leaves with the same largest difference the first one verified is kept. */
+int cattus_hip_verify_stats(cattus_eval* e, cattus_verify_stats* out);
+/* The planes of the leaf that holds max_dlogit, as it was given to the evaluator.  CATTUS_E_STATE before any leaf was verified.
+ * (cattus_hip_compare_outputs() in cattus_hip_diag.h runs the comparison kernel alone, on host arrays.) */
+int cattus_hip_verify_worst_planes(cattus_eval* e, uint64_t* planes /* [planes][plane_words] */);
+
 /* Average device time in microseconds of one 3x3-conv tower launch over `reps` forwards of n
  * leaves.  Every launch carries its own start/stop HIP event pair stamped by the kernel dispatch
  * itself (hipExtLaunchKernelGGL) on the evaluator's stream.  Also returns the number of such

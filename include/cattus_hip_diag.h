@@ -57,6 +57,16 @@ int cattus_hip_stream_shifts(const cattus_eval* e, int* out, uint32_t n);
  * CATTUS_FUSED_STEM=0), 0 where the stem kernel or a one-launch tower expands the planes itself.  Either pointer may be NULL. */
 int cattus_hip_stem_input(const cattus_eval* e, uint32_t* channels, uint32_t* packed);
 
+/* The comparison kernel of cattus_hip_verify (cattus_hip.h) on host arrays, so that tests can feed it what no network produces.
+ * policy_a / policy_b: [n][moves], value_a / value_b: [n], b the reference side; records: n x 16 bytes, per leaf
+ *   f32 the largest |a - b| over the leaf's logits (a NaN difference takes no part; 0 where none is positive)
+ *   u32 the lowest move index that holds it (0 where it is 0)
+ *   f32 |value_a - value_b| (a NaN as 0x7fc00000)
+ *   u32 flags: bit 0 the leaf is outside the bar, bit 1 its value is
+ * The same inputs give the same bytes on every run.  n, moves >= 1. */
+int cattus_hip_compare_outputs(int device, const float* policy_a, const float* policy_b, const float* value_a, const float* value_b,
+                               uint32_t n, uint32_t moves, void* records /* [n][16 bytes] */);
+
 #ifdef __cplusplus
 }
 #endif
