@@ -286,6 +286,9 @@ struct Lane {
     // on the device and in page-locked memory.  (The batch's planes are on the host either way: in the caller's page-locked buffer or in h_planes.)
     DevBuf d_verify;
     PinnedBuf h_verify;
+    // cattus_hip_tap / cattus_hip_trace, allocated on first use: one point's f32 [max_batch][channels][S*S], the [points][max_batch] records, and the
+    // stream shifts as the kernels read them (only where some channel is shifted)
+    DevBuf d_tap, d_trace, d_shifts;
     std::mutex mu;  // held while a batch uses the lane
     ~Lane() {
         if (done) (void)hipEventDestroy(done);
@@ -667,6 +670,16 @@ bool one_launch_now(const cattus_eval* e, uint32_t nb) {
     return e->plan.one_launch && !e->tower_gave_up.load(std::memory_order_relaxed) && wino4_tower_fits(nb, e->fpad, e->cus);
 }
 
+// What cattus_hip_stream_range, cattus_hip_tap and cattus_hip_trace hang behind the layers of a pass.  It is called while the pass is being
+// enqueued, behind every conv layer of the tower and behind the head convs, with the point (include/cattus_hip.h: 0 the stem, 2i + 1 and 2i + 2
+// block i's two convs, the last one the heads), the buffer that layer wrote and where an element lives in it (tap_layout.h); what it enqueues
+// on the pass's stream runs before the next layer overwrites anything.  A pass with an observer runs the per-layer form of its plan's
+// arithmetic -- the resident towers Forward::per_layer on the same ConvLayer buffers, the one-launch Winograd tower its per-layer launches:
+// the same bits (tests/test_tower_plan_gpu.py, tests/test_trace_gpu.py).  Every other call passes none and enqueues what it always did.
+using Observer = std::function<int(uint32_t point, const void* buf, const TapSource& src)>;
+
+uint32_t net_points(const cattus_net_desc& d) { return 2 + 2 * d.blocks; }
+
 // One forward pass being enqueued on `st`: n leaves whose planes are at d_planes (nb boards with the tower's padding), logits and values to
 // d_policy / d_value.  One function per TowerKind; a tower returns its output rows, or nullptr where it has run the head convs itself.
 struct Forward {
@@ -677,10 +690,37 @@ struct Forward {
     float *d_policy, *d_value;
     hipStream_t st;
     TowerTimer* tt;
-    bool observe;  // cattus_hip_stream_range: the range kernel behind every stream tensor of per_layer(); false on every other call
+    const Observer* obs;  // nullptr on every call but cattus_hip_stream_range, cattus_hip_tap and cattus_hip_trace
+    int orc = CATTUS_OK;  // the first failure an observer reported
     const cattus_net_desc& d = e->d;
     const uint32_t w64 = e->cfg.plane_words, S = d.board, F = d.filters, FP = e->fpad;
     float *a = L.a.as<float>(), *t = L.t.as<float>(), *y = L.y.as<float>();
+
+    void seen(uint32_t point, const void* buf, const TapSource& src) {
+        if (!obs) return;
+        const int rc = (*obs)(point, buf, src);
+        if (rc && !orc) orc = rc;
+    }
+    // where tower layer l (the point of the same number) keeps its output: NCHW on the generic path; on the tuned ones rows in the tower's
+    // element type, except that the Winograd tower keeps f32 rows throughout and the f16 towers' last layer writes f32 rows for the heads
+    TapSource tower_source(uint32_t l) const {
+        TapSource s{};
+        s.C = F, s.hw = e->hw, s.slots = e->slots, s.pitch = FP;
+        if (!e->plan.tuned()) s.layout = TAP_NCHW_F32;
+        else if (e->plan.wino()) s.layout = TAP_ROWS_WINO_F32;
+        else if (e->act == Act::F32 || (act_f16_family(e->act) && l == 2 * d.blocks)) s.layout = TAP_ROWS_F32;
+        else s.layout = e->act == Act::BF16 ? TAP_ROWS_BF16 : e->act == Act::F16 ? TAP_ROWS_F16 : TAP_ROWS_F16X2;
+        return s;
+    }
+    // the head convs' output: [leaf][(vhc + phc) * hw] on the generic path, HeadsMfma::hv's two fragment-ordered matrices on the tuned ones
+    TapSource head_source() const {
+        TapSource s{};
+        s.C = d.vhc + d.phc, s.hw = e->hw, s.layout = TAP_NCHW_F32;
+        if (!e->plan.tuned()) return s;
+        s.layout = head_act(e->act) == Act::BF16 ? TAP_HV_BF16 : TAP_HV_F32;
+        s.vhc = d.vhc, s.kvp = e->kvp, s.kpp = e->kpp, s.hv_pol = hv_leaves(e) * e->kvp;
+        return s;
+    }
 
     // with `tt` (a timing pass) each tower launch gets its own (start, stop) event pair stamped by the kernel itself
     hipEvent_t ev() { return tt && tt->used < tt->ev.size() ? tt->ev[tt->used++] : nullptr; }
@@ -703,10 +743,13 @@ struct Forward {
             launch_conv3x3_generic(in, c.w.as<float>(), c.b.as<float>(), res, out, n, cin, F, S, st, s0, s1);
         };
         conv(e->stem, L.x0.as<float>(), d.planes, nullptr, a);
+        seen(0, a, tower_source(0));
         for (uint32_t i = 0; i < d.blocks; i++) {
             conv(*e->c1[i], a, F, nullptr, t);
+            seen(2 * i + 1, t, tower_source(2 * i + 1));
             conv(*e->c2[i], t, F, a, y);
             std::swap(a, y);
+            seen(2 * i + 2, a, tower_source(2 * i + 2));
         }
         return a;
     }
@@ -755,29 +798,34 @@ struct Forward {
                             (e->plan.w_frag ? CONV_W_FRAG : 0) | flags, e->conv_opts);
     }
 
-    // the f32 tower's stream tensor in `a` (plain f32 rows) into the lane's range accumulators
-    void observe_stream() {
-        double* const acc_sq = L.range_acc.as<double>();
-        launch_stream_range(a, nb, n, S, FP, L.range_part_sq.as<double>(), L.range_part_max.as<float>(), acc_sq, reinterpret_cast<float*>(acc_sq + FP), st);
+    // Layer l of the per-layer tower -- 0: the stem; 2i + 1: block i's conv1, a -> t; 2i + 2: its conv2 + skip, t -> y, which becomes a --
+    // in layer order; returns the buffer it wrote.  (cattus_hip_trace steps the shadow's pass through this, one layer per point.)
+    const void* per_layer_step(uint32_t l) {
+        const int last_flags = act_f16_family(e->act) && l == 2 * d.blocks ? CONV_OUT_F32 : 0;  // the f16 towers hand the f32 head kernels plain f32 rows
+        if (l == 0) {
+            conv_mfma(e->stem, L.x0.p, nullptr, a, last_flags, true);
+            return a;
+        }
+        const uint32_t i = (l - 1) / 2;
+        if (l & 1) {
+            conv_mfma(*e->c1[i], a, nullptr, t, 0);
+            return t;
+        }
+        conv_mfma(*e->c2[i], t, a, y, last_flags);
+        std::swap(a, y);
+        return a;
     }
 
     const void* per_layer() {
-        const int last_flags = act_f16_family(e->act) ? CONV_OUT_F32 : 0;  // the f16 towers hand the f32 head kernels plain f32 rows
-        conv_mfma(e->stem, L.x0.p, nullptr, a, d.blocks == 0 ? last_flags : 0, true);
-        if (observe) observe_stream();
-        for (uint32_t i = 0; i < d.blocks; i++) {
-            conv_mfma(*e->c1[i], a, nullptr, t, 0);
-            conv_mfma(*e->c2[i], t, a, y, i + 1 == d.blocks ? last_flags : 0);
-            std::swap(a, y);
-            if (observe) observe_stream();
-        }
+        for (uint32_t l = 0; l <= 2 * d.blocks; l++) seen(l, per_layer_step(l), tower_source(l));
         return a;
     }
 
     // Wino16 / Wino4: the stem on the direct kernel, every layer behind it in Winograd form, f32 rows between the layers
     int wino() {
         conv_mfma(e->stem, L.x0.p, nullptr, a, CONV_OUT_F32 | CONV_WINO_IN, true);
-        if (one_launch_now(e, nb)) {
+        seen(0, a, tower_source(0));
+        if (!obs && one_launch_now(e, nb)) {
             // every layer behind the stem in ONE launch: counters and error word zeroed ahead of it on the same stream, the error word
             // copied to page-locked memory behind it (eval_host reads it when the batch is back; the device entry points at their next call)
             hipEvent_t s0 = ev(), s1 = ev();
@@ -798,10 +846,12 @@ struct Forward {
         };
         for (uint32_t i = 0; i < d.blocks; i++) {
             conv(*e->c1[i], a, nullptr, t);
+            seen(2 * i + 1, t, tower_source(2 * i + 1));
             // in place: the block's output over its own skip rows -- the lane that adds a skip element writes that element, behind all its reads:
             // two activation buffers instead of three (33.6 instead of 50 MB per lane of what a pass drags through the Infinity Cache beside 168 MB of U)
             conv(*e->c2[i], t, a, e->plan.inplace ? a : y);
             if (!e->plan.inplace) std::swap(a, y);
+            seen(2 * i + 2, a, tower_source(2 * i + 2));
         }
         return CATTUS_OK;
     }
@@ -815,6 +865,7 @@ struct Forward {
         hd.w2 = e->w2.as<float>(), hd.b2 = e->b2.as<float>(), hd.value = d_value;
         hd.slots = e->slots, hd.hv_leaves = hv_leaves(e);
         launch_heads_mfma(head_act(e->act), tower, n, FP, hd, st);
+        seen(net_points(d) - 1, L.hv.p, head_source());
     }
 
     void heads_generic(const void* tower) {
@@ -825,14 +876,21 @@ struct Forward {
         launch_value_fc1(L.hv.as<float>(), kv + kp, e->w1t.as<float>(), e->b1.as<float>(), n, kv, L.h1.as<float>(), st);
         launch_value_fc2_tanh(L.h1.as<float>(), e->w2.as<float>(), e->b2.as<float>(), n, d_value, st);
         launch_policy_fc(L.hv.as<float>(), kv + kp, kv, e->wpt.as<float>(), e->bp.as<float>(), n, kp, d.moves, d_policy, st);
+        seen(net_points(d) - 1, L.hv.p, head_source());
     }
 };
 
+// boards of a pass of n leaves with the tower's padding: whole workgroups of the conv kernel on the tuned towers
+uint32_t padded_boards(const cattus_eval* e, uint32_t n) {
+    const uint32_t bpw = e->plan.tuned() ? ROWS_PER_WG / e->slots : 1;
+    return (n + bpw - 1) / bpw * bpw;
+}
+
 int enqueue_forward(cattus_eval* e, Lane& L, const uint64_t* d_planes, uint32_t n, float* d_policy, float* d_value, hipStream_t st, TowerTimer* tt = nullptr,
-                    bool observe = false) {
-    const uint32_t bpw = e->plan.tuned() ? ROWS_PER_WG / e->slots : 1;  // boards per workgroup of the conv kernel
-    Forward f{e, L, d_planes, n, (n + bpw - 1) / bpw * bpw, d_policy, d_value, st, tt, observe};
-    switch (e->plan.kind) {
+                    const Observer* obs = nullptr) {
+    Forward f{e, L, d_planes, n, padded_boards(e, n), d_policy, d_value, st, tt, obs};
+    const bool resident = e->plan.kind == TowerKind::Resident64 || e->plan.kind == TowerKind::Resident64Split;
+    switch (obs && resident ? TowerKind::PerLayer : e->plan.kind) {  // observed: the resident towers' per-layer twin (upload_conv: one layout for both)
         case TowerKind::Simple: f.simple(); break;
         case TowerKind::Generic: f.heads_generic(f.generic()); break;
         case TowerKind::PerLayer: f.heads_mfma(f.per_layer()); break;
@@ -845,7 +903,7 @@ int enqueue_forward(cattus_eval* e, Lane& L, const uint64_t* d_planes, uint32_t 
             break;
     }
     if (hipError_t err = hipGetLastError()) return fail(CATTUS_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(err));
-    return CATTUS_OK;
+    return f.orc;
 }
 
 // seconds: of a batch whose wait was measured; nullptr: the counters alone (an asynchronous entry point measures no time).  verified: the batch
@@ -1315,11 +1373,20 @@ CATTUS_API int cattus_hip_stream_range(cattus_eval* e, const uint64_t* planes, u
     }
     HIP_TRY(hipMemsetAsync(L.range_acc.p, 0, acc_bytes, L.stream));
     const size_t leaf_words = (size_t)d.planes * e->cfg.plane_words;
+    uint32_t m = 0;  // leaves of the chunk being enqueued
+    // the f32 tower's stream tensors (the even points: plain f32 rows) into the lane's range accumulators
+    const Observer range = [&](uint32_t point, const void* buf, const TapSource&) {
+        double* const acc_sq = L.range_acc.as<double>();
+        if (point % 2 == 0)
+            launch_stream_range(static_cast<const float*>(buf), padded_boards(e, m), m, d.board, (uint32_t)FP, L.range_part_sq.as<double>(), L.range_part_max.as<float>(),
+                                acc_sq, reinterpret_cast<float*>(acc_sq + FP), L.stream);
+        return CATTUS_OK;
+    };
     for (uint32_t at = 0; at < n; at += e->cfg.max_batch) {  // the staging buffer is free again once the chunk is through
-        const uint32_t m = std::min(n - at, e->cfg.max_batch);
+        m = std::min(n - at, e->cfg.max_batch);
         memcpy(L.h_planes.p, planes + at * leaf_words, m * leaf_words * 8);
         HIP_TRY(hipMemcpyAsync(L.d_planes.p, L.h_planes.p, m * leaf_words * 8, hipMemcpyHostToDevice, L.stream));
-        if (int rc = enqueue_forward(e, L, L.d_planes.as<uint64_t>(), m, L.d_policy.as<float>(), L.d_value.as<float>(), L.stream, nullptr, true)) return rc;
+        if (int rc = enqueue_forward(e, L, L.d_planes.as<uint64_t>(), m, L.d_policy.as<float>(), L.d_value.as<float>(), L.stream, nullptr, &range)) return rc;
         HIP_TRY(hipStreamSynchronize(L.stream));
     }
     std::vector<double> sq(FP);
@@ -1548,35 +1615,161 @@ CATTUS_API int cattus_hip_stats(cattus_eval* e, cattus_stats* out) {
     return CATTUS_OK;
 }
 
-CATTUS_API int cattus_hip_verify(cattus_eval* e, const void* weights, size_t nbytes, uint32_t every) {
-    if (!e || !weights) return fail(CATTUS_E_INVALID, "NULL argument");
-    if (e->plan.kind == TowerKind::Simple) return fail(CATTUS_E_UNSUPPORTED, "a SimpleTwoHeadedModel runs in f32 whatever its dtype: there is nothing to verify it against");
+namespace {
+
+// What cattus_hip_verify and cattus_hip_trace ask before anything else: is there an exact tower to hold this evaluator to, and is `weights`
+// the blob it was created from (the evaluator keeps no host copy of it)?
+int shadow_args(const cattus_eval* e, const void* weights, size_t nbytes, const char* what) {
+    if (e->plan.kind == TowerKind::Simple) return fail(CATTUS_E_UNSUPPORTED, "a SimpleTwoHeadedModel runs in f32 whatever its dtype: there is nothing to %s it against", what);
     if (e->act == Act::F32) return fail(CATTUS_E_UNSUPPORTED, "a dtype f32 evaluator is the exact tower: its shadow would be itself");
     if (nbytes != e->blob_bytes || blob_hash64(weights, nbytes) != e->blob_hash)
-        return fail(CATTUS_E_INVALID, "verify: this is not the weight blob the evaluator was created from");
+        return fail(CATTUS_E_INVALID, "%s: this is not the weight blob the evaluator was created from", what);
+    return CATTUS_OK;
+}
+
+// The shadow: a dtype f32 evaluator of the same blob on the same device with the same max_batch and plane_words, no switches, that `e` owns.
+// Built by whichever of verify and trace comes first; the caller holds every lane mutex (shadow_args passed).
+int ensure_shadow(cattus_eval* e, const void* weights, size_t nbytes) {
+    if (e->shadow) return CATTUS_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    cattus_eval_config scfg = e->cfg;
+    scfg.dtype = CATTUS_DTYPE_F32, scfg.tower_form = CATTUS_TOWER_AUTO;
+    return create_impl(weights, nbytes, &scfg, nullptr, &e->shadow);  // CATTUS_E_NOMEM where it does not fit
+}
+
+}  // namespace
+
+CATTUS_API int cattus_hip_verify(cattus_eval* e, const void* weights, size_t nbytes, uint32_t every) {
+    if (!e || !weights) return fail(CATTUS_E_INVALID, "NULL argument");
+    if (int rc = shadow_args(e, weights, nbytes, "verify")) return rc;
     std::unique_lock<std::mutex> held[NLANES];  // every lane, in lane order: batches in flight finish first, none starts meanwhile
     for (int i = 0; i < NLANES; i++) held[i] = std::unique_lock<std::mutex>(e->lanes[i].mu);
-    if (every && !e->shadow) {
-        HIP_TRY(hipSetDevice(e->device));
-        // the same blob on the same device with the same max_batch and plane_words, dtype f32, no switches
-        cattus_eval_config scfg = e->cfg;
-        scfg.dtype = CATTUS_DTYPE_F32, scfg.tower_form = CATTUS_TOWER_AUTO;
-        cattus_eval* shadow = nullptr;
-        if (int rc = create_impl(weights, nbytes, &scfg, nullptr, &shadow)) return rc;  // CATTUS_E_NOMEM where it does not fit
+    if (every) {
+        if (int rc = ensure_shadow(e, weights, nbytes)) return rc;
         const size_t bytes = (size_t)e->cfg.max_batch * 2 * sizeof(VerifyRecord);
-        for (Lane& L : e->lanes) {
+        for (Lane& L : e->lanes) {  // (a shadow that trace built first, or one kept from an attempt that ran out of memory here, stays: the evaluator owns it)
             int rc = CATTUS_OK;
             if (!L.d_verify.p) rc = L.d_verify.alloc(bytes);
             if (!rc && !L.h_verify.p) rc = L.h_verify.alloc(bytes);
-            if (rc) {
-                delete shadow;
-                return rc;
-            }
+            if (rc) return rc;
         }
-        e->shadow = shadow;
     }
     e->verify_every = every;  // 0: off -- the record and the shadow stay, and turning it on again goes on counting
     return CATTUS_OK;
+}
+
+CATTUS_API int cattus_hip_points(const cattus_eval* e, uint32_t* points) {
+    if (!e || !points) return fail(CATTUS_E_INVALID, "NULL argument");
+    if (e->plan.kind == TowerKind::Simple) return fail(CATTUS_E_UNSUPPORTED, "a SimpleTwoHeadedModel has no conv layers to observe");
+    *points = net_points(e->d);
+    return CATTUS_OK;
+}
+
+namespace {
+
+// The stream shifts as the observation kernels read them, on lane L; NULL where no channel is shifted (f32, bf16, every seeded network).
+int lane_shifts(cattus_eval* e, Lane& L, const int** out) {
+    *out = nullptr;
+    const std::vector<int>& tk = e->stream_shifts;
+    if (std::none_of(tk.begin(), tk.end(), [](int t) { return t != 0; })) return CATTUS_OK;
+    if (!L.d_shifts.p)
+        if (int rc = L.d_shifts.upload(tk.data(), tk.size() * sizeof(int))) return rc;
+    *out = L.d_shifts.as<int>();
+    return CATTUS_OK;
+}
+
+// n host leaves onto lane L and through the per-layer twin with `obs` behind its layers, enqueued and not waited for.  Not a batch: nothing
+// is counted and no verify ticket is taken (the kernels' own `saturated` counter counts what this pass clamps, as it does for any pass).
+int enqueue_observed(cattus_eval* e, Lane& L, const uint64_t* planes, uint32_t n, const Observer& obs) {
+    const size_t pbytes = (size_t)n * e->d.planes * e->cfg.plane_words * 8;
+    memcpy(L.h_planes.p, planes, pbytes);
+    HIP_TRY(hipMemcpyAsync(L.d_planes.p, L.h_planes.p, pbytes, hipMemcpyHostToDevice, L.stream));
+    return enqueue_forward(e, L, L.d_planes.as<uint64_t>(), n, L.d_policy.as<float>(), L.d_value.as<float>(), L.stream, nullptr, &obs);
+}
+
+// `result` (bytes from d_result) and the pass's own outputs back to the host; returns with the lane's stream drained.
+int collect_observed(cattus_eval* e, Lane& L, uint32_t n, void* result, const void* d_result, size_t bytes, float* policy, float* value) {
+    HIP_TRY(hipMemcpyAsync(result, d_result, bytes, hipMemcpyDeviceToHost, L.stream));
+    if (policy) HIP_TRY(hipMemcpyAsync(L.h_policy.p, L.d_policy.p, (size_t)n * e->d.moves * 4, hipMemcpyDeviceToHost, L.stream));
+    if (value) HIP_TRY(hipMemcpyAsync(L.h_value.p, L.d_value.p, (size_t)n * 4, hipMemcpyDeviceToHost, L.stream));
+    HIP_TRY(hipStreamSynchronize(L.stream));
+    if (policy) memcpy(policy, L.h_policy.p, (size_t)n * e->d.moves * 4);
+    if (value) memcpy(value, L.h_value.p, (size_t)n * 4);
+    return CATTUS_OK;
+}
+
+}  // namespace
+
+CATTUS_API int cattus_hip_tap(cattus_eval* e, const uint64_t* planes, uint32_t n, uint32_t point, float* out, float* policy, float* value) {
+    if (!e || !planes || !out) return fail(CATTUS_E_INVALID, "NULL argument");
+    if (e->plan.kind == TowerKind::Simple) return fail(CATTUS_E_UNSUPPORTED, "a SimpleTwoHeadedModel has no conv layers to tap");
+    const cattus_net_desc& d = e->d;
+    const uint32_t P = net_points(d), ocn = d.vhc + d.phc;
+    if (n < 1 || n > e->cfg.max_batch) return fail(CATTUS_E_INVALID, "invalid sample len %u, 1..=%u", n, e->cfg.max_batch);
+    if (point >= P) return fail(CATTUS_E_INVALID, "tap: point %u, the network has points 0..=%u", point, P - 1);
+    std::unique_lock<std::mutex> lk;
+    Lane& L = take_lane(e, lk);
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if (!L.d_tap.p && (rc = L.d_tap.alloc((size_t)e->cfg.max_batch * std::max(d.filters, ocn) * e->hw * 4))) return rc;
+    const int* shifts = nullptr;
+    if ((rc = lane_shifts(e, L, &shifts))) return rc;
+    size_t bytes = 0;
+    const Observer tap = [&](uint32_t at, const void* buf, const TapSource& src) {
+        if (at != point) return CATTUS_OK;
+        // the residual stream (the even points) is what the f16 towers carry at 2^t_k; the middle activations and the heads are at 2^0
+        launch_tap(buf, src, at % 2 == 0 ? shifts : nullptr, n, L.d_tap.as<float>(), L.stream);
+        bytes = (size_t)n * src.C * src.hw * 4;
+        return CATTUS_OK;
+    };
+    if ((rc = enqueue_observed(e, L, planes, n, tap))) return rc;
+    if (!bytes) return fail(CATTUS_E_STATE, "tap: the pass never reached point %u", point);
+    return collect_observed(e, L, n, out, L.d_tap.p, bytes, policy, value);
+}
+
+CATTUS_API int cattus_hip_trace(cattus_eval* e, const void* weights, size_t nbytes, const uint64_t* planes, uint32_t n, cattus_trace_record* out, uint32_t points,
+                                float* policy, float* value) {
+    static_assert(sizeof(cattus_trace_record) == sizeof(TraceRecord) && offsetof(cattus_trace_record, rms_diff) == offsetof(TraceRecord, rms_diff) &&
+                      offsetof(cattus_trace_record, flags) == offsetof(TraceRecord, flags),
+                  "the kernel's record is the header's");
+    if (!e || !weights || !planes || !out) return fail(CATTUS_E_INVALID, "NULL argument");
+    if (int rc = shadow_args(e, weights, nbytes, "trace")) return rc;
+    const cattus_net_desc& d = e->d;
+    const uint32_t P = net_points(d);
+    if (points != P) return fail(CATTUS_E_INVALID, "trace: records for %u points asked for, the network has %u", points, P);
+    if (n < 1 || n > e->cfg.max_batch) return fail(CATTUS_E_INVALID, "invalid sample len %u, 1..=%u", n, e->cfg.max_batch);
+    {
+        std::unique_lock<std::mutex> held[NLANES];  // as cattus_hip_verify: the shadow changes only with every lane mutex held
+        for (int i = 0; i < NLANES; i++) held[i] = std::unique_lock<std::mutex>(e->lanes[i].mu);
+        if (int rc = ensure_shadow(e, weights, nbytes)) return rc;
+    }
+    cattus_eval* const sh = e->shadow;  // never replaced once built
+    if (sh->plan.kind != TowerKind::PerLayer || sh->slots != e->slots) return fail(CATTUS_E_UNSUPPORTED, "trace: the f32 shadow of this network is not a per-layer MFMA tower");
+    std::unique_lock<std::mutex> lk;
+    Lane& L = take_lane(e, lk);
+    Lane& SL = sh->lanes[&L - e->lanes];  // used under this evaluator's lane mutex and by nobody else, as in a verified batch
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if (!L.d_trace.p && (rc = L.d_trace.alloc((size_t)P * e->cfg.max_batch * sizeof(TraceRecord)))) return rc;
+    const int* shifts = nullptr;
+    if ((rc = lane_shifts(e, L, &shifts))) return rc;
+    // The shadow's f32 per-layer pass on the same device-resident leaves, advanced one layer per point of the evaluator's pass, on the same
+    // stream: behind layer l of both the compare kernel reads the two buffers before either pass overwrites them.  Nothing grows with the
+    // number of points but the records.
+    Forward sf{sh, SL, L.d_planes.as<uint64_t>(), n, padded_boards(sh, n), SL.d_policy.as<float>(), SL.d_value.as<float>(), L.stream, nullptr, nullptr};
+    const Observer lockstep = [&](uint32_t at, const void* buf, const TapSource& src) {
+        TraceRecord* const rec = L.d_trace.as<TraceRecord>() + (size_t)at * n;
+        if (at + 1 < P) {
+            const void* ref = sf.per_layer_step(at);
+            launch_trace_compare(buf, src, at % 2 == 0 ? shifts : nullptr, ref, sf.tower_source(at), n, rec, L.stream);
+        } else {
+            sf.heads_mfma(sf.a);
+            launch_trace_compare(buf, src, nullptr, SL.hv.p, sf.head_source(), n, rec, L.stream);
+        }
+        return CATTUS_OK;
+    };
+    if ((rc = enqueue_observed(e, L, planes, n, lockstep))) return rc;
+    return collect_observed(e, L, n, out, L.d_trace.p, (size_t)P * n * sizeof(TraceRecord), policy, value);
 }
 
 CATTUS_API int cattus_hip_verify_stats(cattus_eval* e, cattus_verify_stats* out) {

@@ -5,6 +5,7 @@
 
 #include "frag_index.h"  // split_frag_index, wino_frag_index, WINO_RING_STAGES
 #include "verify_rule.h"  // VerifyRecord and the rule behind it
+#include "tap_layout.h"   // TapSource, TraceRecord: where a point's activations live, the rule of a trace record
 
 namespace cattus {
 
@@ -130,6 +131,16 @@ void launch_stream_range(const float* rows, uint32_t nb, uint32_t n, uint32_t S,
 // same bytes on every run (no atomics).
 void launch_verify_outputs(const float* policy_a, const float* policy_b, const float* value_a, const float* value_b, uint32_t n, uint32_t M,
                            VerifyRecord* records, float* detail, hipStream_t st);
+
+// ---- observation: one point of the network (cattus_hip_tap, cattus_hip_trace; tap_layout.h has the layouts and the record) ----
+// src: the tensor as the evaluator holds it (TapSource), shifts: NULL, or per live channel the exponent t the tensor carries it at (device,
+// s.C ints); out: f32 [n][s.C][s.hw], 16-byte aligned, in network units.  Rows layouts of the tuned towers' padding (pitch % 64 == 0) go
+// through the transposing kernel, everything else through a gather.  Only leaves < n, pixels < hw and channels < C are read into a result.
+void launch_tap(const void* src, const TapSource& s, const int* shifts, uint32_t n, float* out, hipStream_t st);
+// x (layout sx, shifts as above) against ref (layout sref, the f32 shadow's: nothing to divide out), the same C and hw: records [n],
+// 32-byte aligned, one per leaf.  The same inputs give the same bytes on every run (no atomics).
+void launch_trace_compare(const void* x, const TapSource& sx, const int* shifts, const void* ref, const TapSource& sref, uint32_t n, TraceRecord* records,
+                          hipStream_t st);
 
 // Diagnostic: one launch of nothing but back-to-back MFMAs of the tower's kind (F16S: f16, BF16, F32: 32x32x2 f32), four
 // waves on each of `cus` workgroups, iters x 4 MFMAs per wave; `out` holds cus * 256 floats.  Returns the launch's FLOPs.

@@ -16,6 +16,8 @@
 //                                                           (HBM-trivial, once per calibrated evaluator, never per batch)
 //       verify_outputs                                      verification: two runtimes' logits and values of a batch against the reference's
 //                                                           cross-runtime bar, one record per leaf (HBM-trivial, verified batches only)
+//       tap_rows, tap_gather, trace_compare                 observation: one point's activations as f32 NCHW, or against the f32 shadow's,
+//                                                           one record per leaf (HBM-trivial, cattus_hip_tap / cattus_hip_trace only)
 //
 // Arithmetic the kernels reproduce: ConvNetV1.forward in eval mode
 // (reference: training/cattus_train/net_utils.py:4-89) on the tensor planes_to_tensor builds
@@ -2575,6 +2577,159 @@ void launch_verify_outputs(const float* policy_a, const float* policy_b, const f
     if (!n) return;
     hipLaunchKernelGGL(verify_outputs_kernel, dim3((n + 3) / 4), dim3(256), 0, st, policy_a, policy_b, value_a, value_b, n, M, records,
                        reinterpret_cast<f32x4*>(detail));
+}
+
+// ------------------------------------------------------------------------------------------
+// Observation: one point of the network read back (cattus_hip_tap), or held against the f32 shadow's (cattus_hip_trace)
+// ------------------------------------------------------------------------------------------
+// tap_layout.h has every address, the decoding and the record's rule; these kernels only walk it.  Both are HBM-trivial and off
+// the hot path (a diagnostic call, never a batch of eval): nobody has timed them.
+__device__ __forceinline__ uint32_t vec_word(const uint4& q, int w) { return w == 0 ? q.x : w == 1 ? q.y : w == 2 ? q.z : q.w; }
+__device__ __forceinline__ uint16_t vec_half(const uint4& q, int j) { return (uint16_t)(vec_word(q, j >> 1) >> ((j & 1) * 16)); }
+
+// Channels c8 .. c8 + 7 (c8 % 8 == 0) of tower row `row` of a rows layout, decoded exactly, the stream shift not yet divided out:
+// 16-byte loads -- two for f32 rows, one for 2-byte rows, the hi and the lo vector for f16x2 pairs.
+__device__ __forceinline__ void rows_load8(const char* __restrict__ base, const TapSource& s, size_t row, uint32_t c8, float (&v)[8]) {
+    if (s.layout == TAP_ROWS_F32 || s.layout == TAP_ROWS_WINO_F32) {
+        const uint4* at = reinterpret_cast<const uint4*>(base + (row * s.pitch + c8) * 4);
+        const uint4 q0 = at[0], q1 = at[1];
+#pragma unroll
+        for (int j = 0; j < 4; j++) v[j] = __uint_as_float(vec_word(q0, j)), v[4 + j] = __uint_as_float(vec_word(q1, j));
+    } else if (s.layout == TAP_ROWS_F16X2) {
+        const char* at = base + row * s.pitch * 4 + (size_t)(c8 >> 5) * 128 + (c8 & 31) * 2;
+        const uint4 hi = *reinterpret_cast<const uint4*>(at), lo = *reinterpret_cast<const uint4*>(at + TAP_LO_BYTES);
+#pragma unroll
+        for (int j = 0; j < 8; j++) v[j] = tap_widen_f16(vec_half(hi, j)) + tap_widen_f16(vec_half(lo, j));
+    } else {
+        const uint4 q = *reinterpret_cast<const uint4*>(base + (row * s.pitch + c8) * 2);
+        const bool f16 = s.layout == TAP_ROWS_F16;
+#pragma unroll
+        for (int j = 0; j < 8; j++) v[j] = f16 ? tap_widen_f16(vec_half(q, j)) : tap_widen_bf16(vec_half(q, j));
+    }
+}
+
+// Tower rows of any rows layout -> f32 [n][C][hw], a transpose: workgroup = (leaf, 64-channel chunk).  Thread = (row lane t / 8,
+// 8 channels t % 8): the eight threads of a row read its chunk's 256 (2-byte rows: 128) contiguous bytes, a wave eight such rows --
+// whole 128-byte lines -- and only rows p < hw of board `leaf`: nothing of a stale slot, board or (below) channel reaches the result.
+// The tile [64][hw | 1] in LDS: the odd pitch spreads a wave's 64 writes (8 channel octets x 8 pixels) over 64 banks.  The chunk's
+// live channels are one contiguous piece of the output, written as 16-byte vectors from its first 16-byte boundary on (S * S is odd
+// on most boards: the floats in front of the boundary and behind the last whole vector go one by one).  slots is an argument: 64- and
+// 128-slot boards run the same code.
+constexpr int TAP_TILE_FLOATS = 64 * 121;  // hw <= 121 (an 11 x 11 board), pitch = hw | 1 <= 121
+__global__ void __launch_bounds__(256) tap_rows_kernel(const char* __restrict__ src, TapSource s, const int* __restrict__ shifts, float* __restrict__ out) {
+    __shared__ float tile[TAP_TILE_FLOATS];
+    const uint32_t leaf = blockIdx.x, c0 = blockIdx.y * 64, cn = s.C - c0 < 64u ? s.C - c0 : 64u, pitch = s.hw | 1;
+    const uint32_t v8 = threadIdx.x & 7, rl = threadIdx.x >> 3;
+    float scale[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const uint32_t c = c0 + v8 * 8 + j;
+        scale[j] = shifts && c < s.C ? tap_pow2(-shifts[c]) : 1.0f;
+    }
+    for (uint32_t p = rl; p < s.hw; p += 32) {
+        float v[8];
+        rows_load8(src, s, (size_t)leaf * s.slots + p, c0 + v8 * 8, v);
+#pragma unroll
+        for (int j = 0; j < 8; j++) tile[(v8 * 8 + j) * pitch + p] = v[j] * scale[j];
+    }
+    __syncthreads();
+    const uint32_t total = cn * s.hw;
+    const size_t o0 = ((size_t)leaf * s.C + c0) * s.hw;
+    float* const dst = out + o0;
+    uint32_t head = (uint32_t)((4 - (o0 & 3)) & 3);
+    head = head < total ? head : total;
+    const uint32_t nvec = (total - head) / 4, tail = head + nvec * 4;
+    auto at = [&](uint32_t i) { return tile[(i / s.hw) * pitch + i % s.hw]; };
+    if (threadIdx.x < head) dst[threadIdx.x] = at(threadIdx.x);
+    for (uint32_t v = threadIdx.x; v < nvec; v += 256) {
+        const uint32_t i = head + v * 4;
+        *reinterpret_cast<f32x4*>(dst + i) = f32x4{at(i), at(i + 1), at(i + 2), at(i + 3)};
+    }
+    if (threadIdx.x < total - tail) dst[tail + threadIdx.x] = at(tail + threadIdx.x);
+}
+
+// The layouts that are tiny or NCHW already (the head point, the generic tower): one thread per output element, tap_decode.
+__global__ void __launch_bounds__(256) tap_gather_kernel(const char* __restrict__ src, TapSource s, const int* __restrict__ shifts, size_t total,
+                                                         float* __restrict__ out) {
+    const size_t per = (size_t)s.C * s.hw;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const uint32_t r = (uint32_t)(i % per);
+        out[i] = tap_decode(s, src, shifts, (uint32_t)(i / per), r / s.hw, r % s.hw);
+    }
+}
+
+void launch_tap(const void* src, const TapSource& s, const int* shifts, uint32_t n, float* out, hipStream_t st) {
+    if (!n) return;
+    if (tap_is_rows(s.layout) && s.pitch % 64 == 0 && s.C <= s.pitch && s.hw <= 121 && s.hw <= s.slots) {
+        hipLaunchKernelGGL(tap_rows_kernel, dim3(n, (s.C + 63) / 64), dim3(256), 0, st, static_cast<const char*>(src), s, shifts, out);
+        return;
+    }
+    const size_t total = (size_t)n * s.C * s.hw, blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(tap_gather_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, static_cast<const char*>(src), s, shifts,
+                       total, out);
+}
+
+// One point of cattus_hip_trace: the evaluator's tensor xa (layout sa, stream shifts to divide out or NULL) against the shadow's xb
+// (layout sb; an f32 evaluator carries nothing at a power of two), one workgroup and one 32-byte record per leaf.  Two rows layouts:
+// thread = 8 channels of a pixel, 16-byte loads (rows_load8), live pixels and live channel octets only, consecutive threads on
+// consecutive octets of a row; anything else (the head point) element by element through tap_decode.  A thread folds its elements with
+// trace_take, the 256 partials combine through LDS in a fixed tree -- sums in double in that one order, the maximum by the order-free
+// rule -- and thread 0 closes the record and reads x and ref at its index: the bytes depend on the data and the shape alone.  No atomics.
+__global__ void __launch_bounds__(256) trace_compare_kernel(const char* __restrict__ xa, TapSource sa, const int* __restrict__ shifts,
+                                                            const char* __restrict__ xb, TapSource sb, TraceRecord* __restrict__ records) {
+    __shared__ TracePartial part[256];
+    const uint32_t leaf = blockIdx.x, hw = sa.hw, C = sa.C, count = C * hw;
+    TracePartial t = trace_partial();
+    if (tap_is_rows(sa.layout) && tap_is_rows(sb.layout)) {
+        const uint32_t cg = (C + 7) / 8;
+        for (uint32_t u = threadIdx.x; u < hw * cg; u += 256) {
+            const uint32_t p = u / cg, c8 = (u % cg) * 8;
+            float x[8], r[8];
+            rows_load8(xa, sa, (size_t)leaf * sa.slots + p, c8, x);
+            rows_load8(xb, sb, (size_t)leaf * sb.slots + p, c8, r);
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const uint32_t c = c8 + j;
+                if (c < C) trace_take(t, shifts ? x[j] * tap_pow2(-shifts[c]) : x[j], r[j], c * hw + p);
+            }
+        }
+    } else {
+        for (uint32_t i = threadIdx.x; i < count; i += 256)
+            trace_take(t, tap_decode(sa, xa, shifts, leaf, i / hw, i % hw), tap_decode(sb, xb, nullptr, leaf, i / hw, i % hw), i);
+    }
+    part[threadIdx.x] = t;
+    __syncthreads();
+    for (uint32_t off = 128; off; off >>= 1) {
+        if (threadIdx.x < off) {
+            TracePartial a = part[threadIdx.x];
+            trace_combine(a, part[threadIdx.x + off]);
+            part[threadIdx.x] = a;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        TraceRecord r = trace_finish(part[0], count);
+        r.x = tap_decode(sa, xa, shifts, leaf, r.at / hw, r.at % hw);
+        r.ref = tap_decode(sb, xb, nullptr, leaf, r.at / hw, r.at % hw);
+        uint4* const o = reinterpret_cast<uint4*>(records + leaf);
+        o[0] = make_uint4(__float_as_uint(r.max_diff), r.at, __float_as_uint(r.x), __float_as_uint(r.ref));
+        o[1] = make_uint4(__float_as_uint(r.rms_diff), __float_as_uint(r.rms_ref), r.flags, r.reserved);
+    }
+}
+
+void launch_trace_compare(const void* x, const TapSource& sx, const int* shifts, const void* ref, const TapSource& sref, uint32_t n, TraceRecord* records,
+                          hipStream_t st) {
+    if (!n) return;
+    if (sx.C != sref.C || sx.hw != sref.hw || !sx.C || !sx.hw) {  // the two sides are one tensor of one network
+        fprintf(stderr, "cattus: launch_trace_compare: %u x %u against %u x %u\n", sx.C, sx.hw, sref.C, sref.hw);
+        abort();
+    }
+    // the rows walk reads whole channel octets: they must lie inside a row
+    if (tap_is_rows(sx.layout) && tap_is_rows(sref.layout) && (sx.pitch % 8 || sref.pitch % 8 || sx.C > sx.pitch || sref.C > sref.pitch)) {
+        fprintf(stderr, "cattus: launch_trace_compare: rows of %u and %u channels for %u live ones\n", sx.pitch, sref.pitch, sx.C);
+        abort();
+    }
+    hipLaunchKernelGGL(trace_compare_kernel, dim3(n), dim3(256), 0, st, static_cast<const char*>(x), sx, shifts, static_cast<const char*>(ref), sref, records);
 }
 
 // ------------------------------------------------------------------------------------------

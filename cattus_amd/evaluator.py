@@ -56,6 +56,9 @@ ABI_SYMBOLS = [
     "cattus_hip_verify",
     "cattus_hip_verify_stats",
     "cattus_hip_verify_worst_planes",
+    "cattus_hip_points",
+    "cattus_hip_tap",
+    "cattus_hip_trace",
     "cattus_hip_compare_outputs",  # include/cattus_hip_diag.h
     "cattus_hip_create_diag",  # include/cattus_hip_diag.h
     "cattus_hip_create_calibrated_diag",  # include/cattus_hip_diag.h
@@ -130,6 +133,11 @@ class VerifyStats(C.Structure):
 VERIFY_RECORD = np.dtype([("max_dlogit", "<f4"), ("move", "<u4"), ("dvalue", "<f4"), ("flags", "<u4")])
 
 
+# one (point, leaf) of HipEvaluator.trace (include/cattus_hip.h, cattus_trace_record): flags bit 0 a non-finite value on either side
+TRACE_RECORD = np.dtype([("max_diff", "<f4"), ("at", "<u4"), ("x", "<f4"), ("ref", "<f4"), ("rms_diff", "<f4"), ("rms_ref", "<f4"), ("flags", "<u4"),
+                         ("reserved", "<u4")])
+
+
 class NetDescC(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("planes", "board", "moves", "blocks", "filters", "vhc", "phc", "fc_hidden")]
 
@@ -189,6 +197,9 @@ def load_library():
     L.cattus_hip_verify_stats.argtypes = [vp, C.POINTER(VerifyStats)]
     L.cattus_hip_verify_worst_planes.argtypes = [vp, u64p]
     L.cattus_hip_compare_outputs.argtypes = [C.c_int, f32p, f32p, f32p, f32p, C.c_uint32, C.c_uint32, vp]
+    L.cattus_hip_points.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.cattus_hip_tap.argtypes = [vp, u64p, C.c_uint32, C.c_uint32, f32p, f32p, f32p]
+    L.cattus_hip_trace.argtypes = [vp, vp, C.c_size_t, u64p, C.c_uint32, vp, C.c_uint32, f32p, f32p]
     for name in ABI_SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("cattus_hip_last_error", "cattus_hip_version", "cattus_hip_runtime_note", "cattus_hip_host_alloc",
@@ -411,6 +422,43 @@ class HipEvaluator:
         out = np.zeros((self.desc.planes, self.plane_words), dtype=np.uint64)
         _check(self._lib.cattus_hip_verify_worst_planes(self._h, _u64(out)))
         return out
+
+    # -- layer-level observation (include/cattus_hip.h, cattus_hip_tap / cattus_hip_trace) ----
+    def points(self) -> int:
+        """P = 2 + 2 * blocks: point 0 the stem's output, 2i + 1 / 2i + 2 block i behind its first conv / its output, P - 1 the head convs'."""
+        p = C.c_uint32()
+        _check(self._lib.cattus_hip_points(self._h, C.byref(p)))
+        return p.value
+
+    def tap(self, planes, point: int, outputs: bool = False):
+        """The activations at ``point`` for the leaves ``planes`` (at most batch_size): float32 ``[n, C, S, S]`` in the reference's layout and
+        in network units, decoded exactly from whatever this evaluator stores there (C = filters, or vhc + phc at the last point: value
+        channels first).  outputs=True: ``(tap, logits, values)`` of that pass.  Not counted as a batch."""
+        planes = self._planes(planes)
+        n, d = planes.shape[0], self.desc
+        if not 0 <= int(point) < 2**32:
+            raise ValueError(f"tap: point {point}")
+        channels = d.filters if int(point) + 1 < 2 + 2 * d.blocks else d.vhc + d.phc
+        out = np.empty((n, channels, d.board, d.board), dtype=np.float32)
+        policy, value = np.empty((n, d.moves), dtype=np.float32), np.empty((n,), dtype=np.float32)
+        _check(self._lib.cattus_hip_tap(self._h, _u64(planes), n, int(point), _f32(out), _f32(policy) if outputs else None, _f32(value) if outputs else None))
+        return (out, policy, value) if outputs else out
+
+    def trace(self, planes, blob: bytes | None = None, points: int | None = None):
+        """The leaves ``planes`` (at most batch_size) through this evaluator's arithmetic and through the f32 shadow's in lockstep, compared on
+        the device at every point: ``(records, logits, values)``, records a structured array ``[P, n]`` of dtype TRACE_RECORD -- max_diff with
+        its index ``at`` = channel * S * S + pixel and both values there (``ref`` the shadow's), rms_diff and rms_ref over the leaf's
+        elements, flags bit 0 a non-finite value.  The first point whose rms_diff / rms_ref jumps is where the evaluator leaves the exact
+        network.  The shadow is ``verify``'s (built here on first use, from the evaluator's own blob unless ``blob`` is given; the library
+        refuses any other).  Not counted as a batch; refused for dtype f32."""
+        planes = self._planes(planes)
+        n, d = planes.shape[0], self.desc
+        blob = self._blob if blob is None else blob
+        P = 2 + 2 * d.blocks if points is None else int(points)
+        rec = np.zeros((P, n), dtype=TRACE_RECORD)
+        policy, value = np.empty((n, d.moves), dtype=np.float32), np.empty((n,), dtype=np.float32)
+        _check(self._lib.cattus_hip_trace(self._h, blob, len(blob), _u64(planes), n, rec.ctypes.data, P, _f32(policy), _f32(value)))
+        return rec, policy, value
 
     def tower_kernel(self) -> str:
         """Name of the kernel that runs this evaluator's tower."""

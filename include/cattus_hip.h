@@ -225,6 +225,46 @@ int cattus_hip_verify_stats(cattus_eval* e, cattus_verify_stats* out);
  * (cattus_hip_compare_outputs() in cattus_hip_diag.h runs the comparison kernel alone, on host arrays.) */
 int cattus_hip_verify_worst_planes(cattus_eval* e, uint64_t* planes /* [planes][plane_words] */);
 
+/* Layer-level observation.  leaves_outside > 0 or saturated > 0 says that this evaluator left the exact network somewhere; these two calls
+ * say where.  A ConvNetV1 evaluator has P = 1 + 2 * blocks + 1 points:
+ *   point 0        the stem ConvBlock's output (the residual stream), `filters` channels
+ *   point 2i + 1   block i behind conv1 + bn1 + ReLU, `filters` channels
+ *   point 2i + 2   block i's output (the residual stream), `filters` channels
+ *   point P - 1    the two head ConvBlocks' outputs, the value head's channels first, then the policy head's: vhc + phc channels
+ *
+ * cattus_hip_tap returns point `point` of n leaves (1 <= n <= max_batch) as the reference module holds it: f32 [n][C][S][S], in network
+ * units.  Whatever the evaluator stores there -- f32, bf16 or f16 rows, (hi, lo) f16 pairs, the heads' fragment order; a stream channel
+ * carried at 2^t (the f16 towers) -- is decoded exactly (hi + lo in f32, the widening of a bf16 / f16) and multiplied by the exact inverse
+ * of that power of two: a tap is a deterministic bit pattern, not an approximation.  Pixel slots, boards and channels of the evaluator's
+ * padding never reach a result.  policy / value (both may be NULL) receive the logits and values of that pass.
+ *
+ * Every tower plan is observed on the per-layer form of its own arithmetic -- the resident one-launch towers and the one-launch Winograd
+ * tower on the per-layer launches that the equality tests hold them to, bit for bit -- so the outputs are cattus_hip_eval's.  An evaluator
+ * that never calls tap or trace runs what it ran before, on the buffers it had before.
+ *
+ * cattus_hip_trace runs the n leaves through this evaluator's per-layer pass and through the f32 shadow's (cattus_hip_verify's: built on
+ * first use by whichever of the two calls comes first, from `weights`, the blob the evaluator was created from) in lockstep, and compares
+ * the two on the device behind every point: out[point * n + leaf] is one record, `points` the P that the caller sized it for.  Nothing but
+ * the P * n records grows with the number of points.  The same leaves give the same bytes on every run.
+ *
+ * Both calls block, and take a lane as cattus_hip_eval does.  Neither is a batch: batches, positions, full_batches and run_seconds_* do
+ * not count them and no verify ticket is taken; `saturated` does count what their passes clamp (it is the kernels' own counter).
+ *
+ * CATTUS_E_UNSUPPORTED: a SimpleTwoHeadedModel (all three calls); trace on a dtype f32 evaluator (its shadow would be itself).
+ * CATTUS_E_INVALID: another blob than the evaluator's own, point >= P, points != P, n outside 1..=max_batch. */
+int cattus_hip_points(const cattus_eval* e, uint32_t* points);
+int cattus_hip_tap(cattus_eval* e, const uint64_t* planes, uint32_t n, uint32_t point, float* out /* [n][C_point][S][S] */, float* policy,
+                   float* value);
+typedef struct cattus_trace_record {
+    float max_diff; uint32_t at;   /* largest float(|double(x) - double(ref)|) over the leaf's live elements (NaN differences take no part; 0 at
+                                      index 0 where none is positive); at = channel * S * S + pixel, the lowest index on ties */
+    float x, ref;                  /* this evaluator's value and the shadow's there */
+    float rms_diff, rms_ref;       /* sqrt(mean (x - ref)^2), sqrt(mean ref^2) over all live elements, sums in double; a NaN is 0x7fc00000 */
+    uint32_t flags, reserved;      /* bit 0: a non-finite value on either side */
+} cattus_trace_record;
+int cattus_hip_trace(cattus_eval* e, const void* weights, size_t nbytes, const uint64_t* planes, uint32_t n,
+                     cattus_trace_record* out /* [P][n] */, uint32_t points, float* policy, float* value);
+
 /* Average device time in microseconds of one 3x3-conv tower launch over `reps` forwards of n
  * leaves.  Every launch carries its own start/stop HIP event pair stamped by the kernel dispatch
  * itself (hipExtLaunchKernelGGL) on the evaluator's stream.  Also returns the number of such
