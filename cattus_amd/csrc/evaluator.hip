@@ -286,6 +286,11 @@ struct Lane {
     // on the device and in page-locked memory.  (The batch's planes are on the host either way: in the caller's page-locked buffer or in h_planes.)
     DevBuf d_verify;
     PinnedBuf h_verify;
+    // the priors part of it (prior_rule.h), verified cattus_hip_eval_legal batches only: a record per leaf on the device and in page-locked memory
+    // (allocated with d_verify), and the shadow's legal-move softmax [max_batch][prior_stride] (allocated on first use, like d_probs)
+    DevBuf d_prior, d_probs_ref;
+    PinnedBuf h_prior;
+    uint32_t prior_stride = 0;
     // cattus_hip_tap / cattus_hip_trace, allocated on first use: one point's f32 [max_batch][channels][S*S], the [points][max_batch] records, and the
     // stream shifts as the kernels read them (only where some channel is shifted)
     DevBuf d_tap, d_trace, d_shifts;
@@ -391,6 +396,13 @@ struct cattus_eval {
         uint32_t move = 0;
         std::vector<uint64_t> worst_planes;  // of the leaf that holds max_dlogit; empty before any leaf was verified
     } verified;
+    // the priors part of the sticky record (prior_rule.h; cattus_hip_verify_prior_stats), under stat_mu, and the leaf that holds its max_tv
+    PriorStats priors;
+    struct WorstPrior {
+        std::vector<uint64_t> planes;
+        std::vector<uint16_t> legal;  // the leaf's legal list, min(legal_count, legal_stride) entries
+        uint32_t top = 0, top_ref = 0;
+    } worst_prior;
 
     // leaf server
     std::mutex srv_mu;
@@ -976,6 +988,29 @@ void fold_verified(cattus_eval* e, const VerifyRecord* rec, uint32_t n, const ui
     v.leaves += n;
 }
 
+// The priors part of a verified batch, beside fold_verified and like it once per batch, in leaf order: the value pairs of every verified leaf
+// (from the details of `rec`), and -- for a batch that came with legal moves -- its n prior records; the leaf that now holds max_tv leaves
+// its planes, its legal list and both favourites.
+void fold_priors(cattus_eval* e, const VerifyRecord* rec, uint32_t n, const uint64_t* planes, const PriorRecord* prior, const LegalArgs* lg) {
+    const size_t words = (size_t)e->d.planes * e->cfg.plane_words;
+    const float* detail = reinterpret_cast<const float*>(rec + n);
+    std::lock_guard<std::mutex> lk(e->stat_mu);
+    PriorStats& s = e->priors;
+    for (uint32_t i = 0; i < n; i++) prior_fold_value(s, detail[(size_t)i * 4 + 2], detail[(size_t)i * 4 + 3]);
+    if (!lg) {
+        s.batches_without_legal += 1;
+        return;
+    }
+    s.batches += 1;
+    for (uint32_t i = 0; i < n; i++) {
+        if (!prior_fold(s, prior[i])) continue;
+        cattus_eval::WorstPrior& w = e->worst_prior;
+        w.planes.assign(planes + i * words, planes + (i + 1) * words);
+        w.legal.assign(lg->idx + (size_t)i * lg->stride, lg->idx + (size_t)i * lg->stride + prior[i].count);
+        w.top = prior[i].top_a, w.top_ref = prior[i].top_b;
+    }
+}
+
 // Blocking host-buffer evaluation; caller holds no lock.  With `lg` the logits stay on the device and
 // the per-leaf softmax over the legal moves comes back instead (policy is not written).
 int eval_host(cattus_eval* e, const uint64_t* planes, uint32_t n, float* policy, float* value, const LegalArgs* lg = nullptr) {
@@ -1000,6 +1035,10 @@ int eval_host(cattus_eval* e, const uint64_t* planes, uint32_t n, float* policy,
             return arc;
         L.legal_stride = lg->stride;
     }
+    if (lg && verify && (L.prior_stride < lg->stride || !L.d_probs_ref.p)) {
+        if (int arc = L.d_probs_ref.alloc((size_t)e->cfg.max_batch * lg->stride * 4)) return arc;
+        L.prior_stride = lg->stride;
+    }
     const void* src_planes = planes;
     if (!direct) {
         memcpy(L.h_planes.p, planes, pbytes);
@@ -1013,6 +1052,16 @@ int eval_host(cattus_eval* e, const uint64_t* planes, uint32_t n, float* policy,
             if (launch_legal_softmax(L.d_policy.as<float>(), d.moves, L.d_legal_idx.as<uint16_t>(), L.d_legal_cnt.as<uint16_t>(),
                                      lg->stride, n, L.d_probs.as<float>(), L.stream))
                 return fail(CATTUS_E_INVALID, "legal stride %u exceeds 1024", lg->stride);
+            if (verify) {
+                // the priors the exact network would have handed back for the same legal moves, and the two rows compared (prior_rule.h): behind
+                // verify_outputs_kernel on this stream, into buffers of their own
+                Lane& SL = e->shadow->lanes[&L - e->lanes];
+                launch_legal_softmax(SL.d_policy.as<float>(), d.moves, L.d_legal_idx.as<uint16_t>(), L.d_legal_cnt.as<uint16_t>(), lg->stride, n,
+                                     L.d_probs_ref.as<float>(), L.stream);
+                launch_verify_priors(L.d_probs.as<float>(), L.d_probs_ref.as<float>(), L.d_legal_cnt.as<uint16_t>(), L.d_value.as<float>(),
+                                     SL.d_value.as<float>(), n, lg->stride, L.d_prior.as<PriorRecord>(), L.stream);
+                HIP_TRY(hipMemcpyAsync(L.h_prior.p, L.d_prior.p, (size_t)n * sizeof(PriorRecord), hipMemcpyDeviceToHost, L.stream));
+            }
             HIP_TRY(hipMemcpyAsync(lg->probs, L.d_probs.p, (size_t)n * lg->stride * 4, hipMemcpyDeviceToHost, L.stream));
         } else {
             HIP_TRY(hipMemcpyAsync(direct ? (void*)policy : L.h_policy.p, L.d_policy.p, (size_t)n * d.moves * 4, hipMemcpyDeviceToHost, L.stream));
@@ -1053,7 +1102,10 @@ int eval_host(cattus_eval* e, const uint64_t* planes, uint32_t n, float* policy,
         if (!lg) memcpy(policy, L.h_policy.p, (size_t)n * d.moves * 4);
         memcpy(value, L.h_value.p, (size_t)n * 4);
     }
-    if (verify) fold_verified(e, L.h_verify.as<VerifyRecord>(), n, static_cast<const uint64_t*>(src_planes));
+    if (verify) {
+        fold_verified(e, L.h_verify.as<VerifyRecord>(), n, static_cast<const uint64_t*>(src_planes));
+        fold_priors(e, L.h_verify.as<VerifyRecord>(), n, static_cast<const uint64_t*>(src_planes), L.h_prior.as<PriorRecord>(), lg);
+    }
     const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     account(e, n, &seconds, verify);
     return CATTUS_OK;
@@ -1651,6 +1703,8 @@ CATTUS_API int cattus_hip_verify(cattus_eval* e, const void* weights, size_t nby
             int rc = CATTUS_OK;
             if (!L.d_verify.p) rc = L.d_verify.alloc(bytes);
             if (!rc && !L.h_verify.p) rc = L.h_verify.alloc(bytes);
+            if (!rc && !L.d_prior.p) rc = L.d_prior.alloc((size_t)e->cfg.max_batch * sizeof(PriorRecord));
+            if (!rc && !L.h_prior.p) rc = L.h_prior.alloc((size_t)e->cfg.max_batch * sizeof(PriorRecord));
             if (rc) return rc;
         }
     }
@@ -1788,6 +1842,59 @@ CATTUS_API int cattus_hip_verify_worst_planes(cattus_eval* e, uint64_t* planes) 
     std::lock_guard<std::mutex> lk(e->stat_mu);
     if (e->verified.worst_planes.empty()) return fail(CATTUS_E_STATE, "no leaf has been verified yet");
     std::copy(e->verified.worst_planes.begin(), e->verified.worst_planes.end(), planes);
+    return CATTUS_OK;
+}
+
+CATTUS_API int cattus_hip_verify_prior_stats(cattus_eval* e, cattus_prior_stats* out) {
+    if (!e || !out) return fail(CATTUS_E_INVALID, "NULL argument");
+    if (out->struct_size != sizeof(cattus_prior_stats)) return fail(CATTUS_E_INVALID, "cattus_prior_stats.struct_size mismatch");
+    if (e->plan.kind == TowerKind::Simple || e->act == Act::F32)
+        return fail(CATTUS_E_UNSUPPORTED, "a dtype f32 evaluator and a SimpleTwoHeadedModel have no shadow to compare priors with");
+    std::lock_guard<std::mutex> lk(e->stat_mu);
+    const PriorStats& s = e->priors;
+    *out = cattus_prior_stats{};
+    out->struct_size = (uint32_t)sizeof(cattus_prior_stats);
+    out->batches = s.batches, out->batches_without_legal = s.batches_without_legal, out->leaves = s.leaves, out->top1_flips = s.top1_flips;
+    out->nonfinite = s.nonfinite, out->empty = s.empty, out->sum_tv = s.sum_tv, out->sum_regret = s.sum_regret;
+    out->max_tv = s.max_tv, out->max_regret = s.max_regret, out->value_leaves = s.value_leaves, out->sum_dvalue = s.sum_dvalue;
+    static_assert(sizeof(out->tv_hist) == sizeof(s.tv_hist), "eight buckets on both sides");
+    memcpy(out->tv_hist, s.tv_hist, sizeof(s.tv_hist));
+    return CATTUS_OK;
+}
+
+CATTUS_API int cattus_hip_verify_worst_prior(cattus_eval* e, uint64_t* planes, uint16_t* legal_idx, uint32_t cap, uint32_t* legal_count, uint32_t* top,
+                                             uint32_t* top_ref) {
+    if (!e || !planes || !legal_idx || !legal_count || !top || !top_ref) return fail(CATTUS_E_INVALID, "NULL argument");
+    if (e->plan.kind == TowerKind::Simple || e->act == Act::F32)
+        return fail(CATTUS_E_UNSUPPORTED, "a dtype f32 evaluator and a SimpleTwoHeadedModel have no shadow to compare priors with");
+    std::lock_guard<std::mutex> lk(e->stat_mu);
+    const cattus_eval::WorstPrior& w = e->worst_prior;
+    if (!e->priors.seeded) return fail(CATTUS_E_STATE, "no leaf's priors have been compared yet");
+    if (cap < w.legal.size()) return fail(CATTUS_E_INVALID, "verify_worst_prior: the leaf has %zu legal moves, cap is %u", w.legal.size(), cap);
+    std::copy(w.planes.begin(), w.planes.end(), planes);
+    std::copy(w.legal.begin(), w.legal.end(), legal_idx);
+    *legal_count = (uint32_t)w.legal.size(), *top = w.top, *top_ref = w.top_ref;
+    return CATTUS_OK;
+}
+
+CATTUS_API int cattus_hip_compare_priors(int device, const float* probs_a, const float* probs_b, const uint16_t* legal_count, uint32_t n, uint32_t L,
+                                         const float* value_a, const float* value_b, void* records) {
+    if (!probs_a || !probs_b || !legal_count || !value_a || !value_b || !records) return fail(CATTUS_E_INVALID, "NULL argument");
+    if (n < 1 || L < 1 || L > 1024 || n > (1u << 20)) return fail(CATTUS_E_INVALID, "compare_priors: %u leaves of stride %u", n, L);
+    int ndev = 0;
+    hipError_t herr = hipGetDeviceCount(&ndev);
+    if (herr != hipSuccess || device < 0 || device >= ndev)
+        return fail(CATTUS_E_DEVICE, "no usable HIP device %d (%s); this library has no CPU path", device, hipGetErrorString(herr));
+    HIP_TRY(hipSetDevice(device));
+    DevBuf pa, pb, cnt, va, vb, rec;
+    int rc;
+    const size_t pbytes = (size_t)n * L * 4;
+    if ((rc = pa.upload(probs_a, pbytes)) || (rc = pb.upload(probs_b, pbytes)) || (rc = cnt.upload(legal_count, (size_t)n * 2)) ||
+        (rc = va.upload(value_a, (size_t)n * 4)) || (rc = vb.upload(value_b, (size_t)n * 4)) || (rc = rec.alloc((size_t)n * sizeof(PriorRecord))))
+        return rc;
+    launch_verify_priors(pa.as<float>(), pb.as<float>(), cnt.as<uint16_t>(), va.as<float>(), vb.as<float>(), n, L, rec.as<PriorRecord>(), nullptr);
+    if (hipError_t err = hipGetLastError()) return fail(CATTUS_E_DEVICE, "kernel launch failed: %s", hipGetErrorString(err));
+    HIP_TRY(hipMemcpy(records, rec.p, (size_t)n * sizeof(PriorRecord), hipMemcpyDeviceToHost));
     return CATTUS_OK;
 }
 

@@ -5,6 +5,7 @@
 
 #include "frag_index.h"  // split_frag_index, wino_frag_index, WINO_RING_STAGES
 #include "verify_rule.h"  // VerifyRecord and the rule behind it
+#include "prior_rule.h"   // PriorRecord and the rule behind it
 #include "tap_layout.h"   // TapSource, TraceRecord: where a point's activations live, the rule of a trace record
 
 namespace cattus {
@@ -131,6 +132,11 @@ void launch_stream_range(const float* rows, uint32_t nb, uint32_t n, uint32_t S,
 // same bytes on every run (no atomics).
 void launch_verify_outputs(const float* policy_a, const float* policy_b, const float* value_a, const float* value_b, uint32_t n, uint32_t M,
                            VerifyRecord* records, float* detail, hipStream_t st);
+
+// probs_a / probs_b: [n][L] legal-move softmax rows of the evaluator and of its shadow (launch_legal_softmax on either's logits), cnt: [n]
+// legal counts, value_a / value_b: [n]; records: [n], one prior_rule.h record per leaf.  The same inputs give the same bytes on every run.
+void launch_verify_priors(const float* probs_a, const float* probs_b, const uint16_t* cnt, const float* value_a, const float* value_b, uint32_t n,
+                          uint32_t L, PriorRecord* records, hipStream_t st);
 
 // ---- observation: one point of the network (cattus_hip_tap, cattus_hip_trace; tap_layout.h has the layouts and the record) ----
 // src: the tensor as the evaluator holds it (TapSource), shifts: NULL, or per live channel the exponent t the tensor carries it at (device,

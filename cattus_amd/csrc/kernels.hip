@@ -16,6 +16,8 @@
 //                                                           (HBM-trivial, once per calibrated evaluator, never per batch)
 //       verify_outputs                                      verification: two runtimes' logits and values of a batch against the reference's
 //                                                           cross-runtime bar, one record per leaf (HBM-trivial, verified batches only)
+//       verify_priors                                       the same batch's legal-move priors against the shadow's: total variation, favourites,
+//                                                           regret, one record per leaf (HBM-trivial, verified eval_legal batches only)
 //       tap_rows, tap_gather, trace_compare                 observation: one point's activations as f32 NCHW, or against the f32 shadow's,
 //                                                           one record per leaf (HBM-trivial, cattus_hip_tap / cattus_hip_trace only)
 //
@@ -2577,6 +2579,40 @@ void launch_verify_outputs(const float* policy_a, const float* policy_b, const f
     if (!n) return;
     hipLaunchKernelGGL(verify_outputs_kernel, dim3((n + 3) / 4), dim3(256), 0, st, policy_a, policy_b, value_a, value_b, n, M, records,
                        reinterpret_cast<f32x4*>(detail));
+}
+
+// The priors a search receives (prior_rule.h): one wave per leaf, four leaves per workgroup, as above.  pa / pb: [n][L] probs rows of this
+// evaluator and of legal_softmax_kernel on the shadow's logits; L may be odd, so a row need not start on a 16-byte boundary, and at <= 1024
+// floats per row the traffic is trivial: plain 4-byte loads, lane l takes k = l, l + 64, ...  The double sum of a lane's |pa - pb| and
+// the butterfly that folds the 64 are prior_rule.h's (the order is part of the rule: the host restates the bytes); favourites and the
+// largest difference combine order-free.  Lane 0 writes the 32-byte record; no atomics, the same bytes on every run.
+__global__ void __launch_bounds__(256) verify_priors_kernel(const float* __restrict__ pa, const float* __restrict__ pb, const uint16_t* __restrict__ cnt,
+                                                            const float* __restrict__ value_a, const float* __restrict__ value_b, uint32_t n, uint32_t L,
+                                                            PriorRecord* __restrict__ records) {
+    const uint32_t lane = threadIdx.x & 63, leaf = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (leaf >= n) return;  // whole waves leave: nothing below synchronises across waves
+    const float* ra = pa + (size_t)leaf * L;
+    const float* rb = pb + (size_t)leaf * L;
+    const uint32_t count = cnt[leaf], c = count < L ? count : L;
+    PriorPartial p;
+    for (uint32_t k = lane; k < c; k += PRIOR_LANES) prior_take(p, ra[k], rb[k], k);
+    double s = prior_lane_sum(ra, rb, c, lane);
+    for (int off = 32; off; off >>= 1) {
+        PriorPartial o;
+        o.a = __shfl_xor(p.a, off), o.ia = (uint32_t)__shfl_xor((int)p.ia, off);
+        o.b = __shfl_xor(p.b, off), o.ib = (uint32_t)__shfl_xor((int)p.ib, off);
+        o.d = __shfl_xor(p.d, off), o.id = (uint32_t)__shfl_xor((int)p.id, off);
+        o.nonfinite = __shfl_xor((int)p.nonfinite, off) != 0;
+        prior_merge(p, o);
+        s = prior_combine(s, __shfl_xor(s, off));  // a double travels as its two 32-bit halves
+    }
+    if (lane == 0) records[leaf] = prior_record(p, s, rb, count, L, value_a[leaf], value_b[leaf]);
+}
+
+void launch_verify_priors(const float* pa, const float* pb, const uint16_t* cnt, const float* value_a, const float* value_b, uint32_t n, uint32_t L,
+                          PriorRecord* records, hipStream_t st) {
+    if (!n) return;
+    hipLaunchKernelGGL(verify_priors_kernel, dim3((n + 3) / 4), dim3(256), 0, st, pa, pb, cnt, value_a, value_b, n, L, records);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -56,10 +56,13 @@ ABI_SYMBOLS = [
     "cattus_hip_verify",
     "cattus_hip_verify_stats",
     "cattus_hip_verify_worst_planes",
+    "cattus_hip_verify_prior_stats",
+    "cattus_hip_verify_worst_prior",
     "cattus_hip_points",
     "cattus_hip_tap",
     "cattus_hip_trace",
     "cattus_hip_compare_outputs",  # include/cattus_hip_diag.h
+    "cattus_hip_compare_priors",  # include/cattus_hip_diag.h
     "cattus_hip_create_diag",  # include/cattus_hip_diag.h
     "cattus_hip_create_calibrated_diag",  # include/cattus_hip_diag.h
     "cattus_hip_stream_shift",  # include/cattus_hip_diag.h
@@ -127,6 +130,31 @@ class VerifyStats(C.Structure):
         ("reserved", C.c_uint32),
     ]
 
+
+class PriorStats(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("batches", C.c_uint64),
+        ("batches_without_legal", C.c_uint64),
+        ("leaves", C.c_uint64),
+        ("top1_flips", C.c_uint64),
+        ("nonfinite", C.c_uint64),
+        ("empty", C.c_uint64),
+        ("sum_tv", C.c_double),
+        ("sum_regret", C.c_double),
+        ("max_tv", C.c_float),
+        ("max_regret", C.c_float),
+        ("tv_hist", C.c_uint64 * 8),
+        ("value_leaves", C.c_uint64),
+        ("sum_dvalue", C.c_double),
+    ]
+
+
+# one leaf of the prior comparison kernel (include/cattus_hip_diag.h, cattus_hip_compare_priors): flags bit 0 a non-finite probability,
+# bit 1 no legal move, bit 2 legal_count > L, bit 3 a non-finite value
+PRIOR_RECORD = np.dtype([("tv", "<f4"), ("top_a", "<u4"), ("top_b", "<u4"), ("regret", "<f4"), ("max_dp", "<f4"), ("k_max", "<u4"), ("count", "<u2"),
+                         ("flags", "<u2"), ("dvalue", "<f4")])
 
 # one leaf's verdict of the comparison kernel (include/cattus_hip_diag.h, cattus_hip_compare_outputs): flags bit 0 the leaf is
 # outside the bar, bit 1 its value is
@@ -197,6 +225,10 @@ def load_library():
     L.cattus_hip_verify_stats.argtypes = [vp, C.POINTER(VerifyStats)]
     L.cattus_hip_verify_worst_planes.argtypes = [vp, u64p]
     L.cattus_hip_compare_outputs.argtypes = [C.c_int, f32p, f32p, f32p, f32p, C.c_uint32, C.c_uint32, vp]
+    u32p = C.POINTER(C.c_uint32)
+    L.cattus_hip_verify_prior_stats.argtypes = [vp, C.POINTER(PriorStats)]
+    L.cattus_hip_verify_worst_prior.argtypes = [vp, u64p, u16p, C.c_uint32, u32p, u32p, u32p]
+    L.cattus_hip_compare_priors.argtypes = [C.c_int, f32p, f32p, u16p, C.c_uint32, C.c_uint32, f32p, f32p, vp]
     L.cattus_hip_points.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.cattus_hip_tap.argtypes = [vp, u64p, C.c_uint32, C.c_uint32, f32p, f32p, f32p]
     L.cattus_hip_trace.argtypes = [vp, vp, C.c_size_t, u64p, C.c_uint32, vp, C.c_uint32, f32p, f32p]
@@ -243,6 +275,21 @@ def compare_outputs(policy_a, policy_b, value_a, value_b, device: int = 0) -> np
         raise ValueError("compare_outputs: policies [n, M] and values [n] of both sides")
     out = np.zeros(pa.shape[0], dtype=VERIFY_RECORD)
     _check(load_library().cattus_hip_compare_outputs(device, _f32(pa), _f32(pb), _f32(va), _f32(vb), pa.shape[0], pa.shape[1], out.ctypes.data))
+    return out
+
+
+def compare_priors(probs_a, probs_b, legal_count, value_a, value_b, device: int = 0) -> np.ndarray:
+    """The prior comparison kernel of ``HipEvaluator.verify_prior_stats`` on host arrays (cattus_hip_compare_priors,
+    include/cattus_hip_diag.h): float32 ``[n, L]`` legal-move softmax rows of two runtimes, b the reference side, uint16 ``[n]`` legal
+    counts and ``[n]`` values -> ``[n]`` records of dtype PRIOR_RECORD."""
+    pa, pb = (np.ascontiguousarray(p, dtype=np.float32) for p in (probs_a, probs_b))
+    va, vb = (np.ascontiguousarray(v, dtype=np.float32) for v in (value_a, value_b))
+    cnt = np.ascontiguousarray(legal_count, dtype=np.uint16)
+    if pa.ndim != 2 or pa.shape != pb.shape or va.shape != (pa.shape[0],) or vb.shape != va.shape or cnt.shape != va.shape:
+        raise ValueError("compare_priors: probs [n, L] of both sides, legal counts [n] and values [n] of both sides")
+    out = np.zeros(pa.shape[0], dtype=PRIOR_RECORD)
+    _check(load_library().cattus_hip_compare_priors(device, _f32(pa), _f32(pb), cnt.ctypes.data_as(C.POINTER(C.c_uint16)), pa.shape[0], pa.shape[1],
+                                                    _f32(va), _f32(vb), out.ctypes.data))
     return out
 
 
@@ -422,6 +469,32 @@ class HipEvaluator:
         out = np.zeros((self.desc.planes, self.plane_words), dtype=np.uint64)
         _check(self._lib.cattus_hip_verify_worst_planes(self._h, _u64(out)))
         return out
+
+    def verify_prior_stats(self) -> dict:
+        """The priors part of the sticky record (cattus_prior_stats): what the verified ``eval_legal`` batches' legal-move priors and every
+        verified batch's values differ by from the exact network's -- batches, batches_without_legal, leaves, top1_flips, nonfinite, empty,
+        sum_tv, sum_regret, max_tv, max_regret, tv_hist (upper edges 1e-7 .. 1e-1, inf), value_leaves, sum_dvalue -- and derived from them
+        tv_mean and regret_mean over the leaves that entered the sums and dvalue_mean over value_leaves (0.0 where there are none)."""
+        s = PriorStats(struct_size=C.sizeof(PriorStats))
+        _check(self._lib.cattus_hip_verify_prior_stats(self._h, C.byref(s)))
+        out = {name: getattr(s, name) for name, _ in PriorStats._fields_ if name not in ("struct_size", "reserved", "tv_hist")}
+        out["tv_hist"] = list(s.tv_hist)
+        summed = s.leaves - s.nonfinite - s.empty
+        out["tv_mean"] = s.sum_tv / summed if summed else 0.0
+        out["regret_mean"] = s.sum_regret / summed if summed else 0.0
+        out["dvalue_mean"] = s.sum_dvalue / s.value_leaves if s.value_leaves else 0.0
+        return out
+
+    def verify_worst_prior(self, cap: int = 1024) -> dict:
+        """The leaf that holds max_tv: ``planes`` uint64 ``[C, plane_words]``, ``legal_idx`` uint16 ``[count]``, ``top`` and ``top_ref``, this
+        evaluator's favourite and the exact network's as positions in that list (raises with status CATTUS_E_STATE before any leaf was
+        compared, CATTUS_E_INVALID when ``cap`` is below the leaf's legal count)."""
+        planes = np.zeros((self.desc.planes, self.plane_words), dtype=np.uint64)
+        legal = np.zeros((max(int(cap), 1),), dtype=np.uint16)
+        count, top, top_ref = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(self._lib.cattus_hip_verify_worst_prior(self._h, _u64(planes), legal.ctypes.data_as(C.POINTER(C.c_uint16)), int(cap), C.byref(count),
+                                                       C.byref(top), C.byref(top_ref)))
+        return {"planes": planes, "legal_idx": legal[: count.value].copy(), "top": top.value, "top_ref": top_ref.value}
 
     # -- layer-level observation (include/cattus_hip.h, cattus_hip_tap / cattus_hip_trace) ----
     def points(self) -> int:

@@ -543,7 +543,10 @@ def write_summary(path, summary: dict):
         },
     }
     # model.inference.verify_every: what the shadow f32 tower found (HipEvaluator.verify_stats), summed over the models that played
-    for key in ("verified_leaves", "leaves_outside_bar", "max_dlogit", "max_dvalue"):
+    # with model.inference.device_softmax too: the priors and values a search received against the exact network's
+    # (HipEvaluator.verify_prior_stats)
+    for key in ("verified_leaves", "leaves_outside_bar", "max_dlogit", "max_dvalue", "prior_leaves", "prior_top1_flips", "prior_tv_mean",
+                "prior_tv_max", "value_abs_diff_mean"):
         if key in summary:
             out["metrics"]["model." + key] = summary[key]
     with open(path, "x") as f:  # create_new, as the reference
@@ -575,6 +578,8 @@ def main(argv=None):
     cfg = config_from_engine_json(engine, concurrent_games=engine.get("concurrent_games", 0))
     # optional: check every Nth batch against a shadow f32 tower (include/cattus_hip.h, cattus_hip_verify); absent or 0: no check
     verify_every = int(inf.get("verify_every", 0))
+    # optional: calc_moves_probs on the device (cattus_hip_eval_legal; Net.hip(..., device_softmax=True)); absent or false: on the host
+    device_softmax = bool(inf.get("device_softmax", False))
 
     def load(path):
         blob = Path(path).read_bytes()
@@ -584,8 +589,8 @@ def main(argv=None):
     ev1 = load(args.model1_path)
     same = os.path.abspath(args.model1_path) == os.path.abspath(args.model2_path)
     ev2 = None if same else load(args.model2_path)
-    res = run_self_play(args.game, cfg, Net.hip(ev1), None if same else Net.hip(ev2), args.games_num, args.out_dir1,
-                        args.out_dir2, keep_records=False)
+    res = run_self_play(args.game, cfg, Net.hip(ev1, device_softmax), None if same else Net.hip(ev2, device_softmax), args.games_num,
+                        args.out_dir1, args.out_dir2, keep_records=False)
     # the f16 towers clamp what leaves the f16 range (cattus_stats.saturated): say so once, and put it in the summary
     res["saturated"] = sum(int(ev.stats().get("saturated", 0)) for ev in (ev1, ev2) if ev is not None)
     if res["saturated"]:
@@ -605,6 +610,21 @@ def main(argv=None):
             print(f"{Path(sys.argv[0]).name}: WARNING: {res['leaves_outside_bar']} of {res['verified_leaves']} verified leaves are outside the "
                   f"reference's cross-runtime tolerance of the f32 tower (max |dlogit| {res['max_dlogit']:.3g}, max |dvalue| {res['max_dvalue']:.3g}): "
                   f"use \"dtype\": \"f32\" in model.inference, or calibrate", file=sys.stderr)
+    if verify_every and device_softmax:
+        ps = [ev.verify_prior_stats() for ev in (ev1, ev2) if ev is not None]
+        summed = sum(p["leaves"] - p["nonfinite"] - p["empty"] for p in ps)
+        value_leaves = sum(p["value_leaves"] for p in ps)
+        res["prior_leaves"] = sum(p["leaves"] for p in ps)
+        res["prior_top1_flips"] = sum(p["top1_flips"] for p in ps)
+        res["prior_tv_mean"] = sum(p["sum_tv"] for p in ps) / summed if summed else 0.0
+        res["prior_tv_max"] = max(p["max_tv"] for p in ps)
+        res["value_abs_diff_mean"] = sum(p["sum_dvalue"] for p in ps) / value_leaves if value_leaves else 0.0
+        if res["prior_top1_flips"]:
+            import sys
+
+            print(f"{Path(sys.argv[0]).name}: NOTE: on {res['prior_top1_flips']} of {res['prior_leaves']} verified leaves the favourite move of dtype "
+                  f"{inf.get('dtype', 'f16x2')!r} is not the f32 tower's (mean prior total variation {res['prior_tv_mean']:.3g}, max "
+                  f"{res['prior_tv_max']:.3g})", file=sys.stderr)
     if args.summary_file:
         write_summary(args.summary_file, res)
 

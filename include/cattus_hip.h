@@ -225,6 +225,51 @@ int cattus_hip_verify_stats(cattus_eval* e, cattus_verify_stats* out);
  * (cattus_hip_compare_outputs() in cattus_hip_diag.h runs the comparison kernel alone, on host arrays.) */
 int cattus_hip_verify_worst_planes(cattus_eval* e, uint64_t* planes /* [planes][plane_words] */);
 
+/* The same verification in the quantities a PUCT search consumes.  The logit bar above is the reference's cross-runtime tolerance: a bf16 or
+ * f16 evaluator (8 and 11 significant bits) is outside it on practically every leaf by construction, so leaves_outside == leaves tells
+ * nothing about them.  A search consumes the softmax over the leaf's legal moves (calc_moves_probs, engine/src/net/mod.rs:100-119) and the
+ * value; this record compares those, per leaf, on the device.
+ *
+ * What feeds it.  A verified batch (ticket % every == 0, as above) of cattus_hip_eval_legal: behind the logit comparison the shadow's logits
+ * go through the same legal-move softmax with the same legal_idx / legal_count, and the two probs rows -- pa, what the call returns, and
+ * pb, what the exact network would have returned -- are compared per leaf over k < c = min(legal_count, legal_stride):
+ *   tv      = float(0.5 sum_k |pa[k] - pb[k]|), the total-variation distance, summed in double in a fixed order (prior_rule.h: the bytes
+ *             can be restated on a CPU)
+ *   regret  = pb[top_ref] - pb[top]: the prior mass the exact network's favourite loses; top / top_ref are the positions in the legal
+ *             list of the largest pa / pb, the lowest on ties; exactly 0 when they agree, >= 0 otherwise
+ * A leaf with a non-finite probability on either side is counted in `nonfinite`, one with legal_count == 0 in `empty`; neither enters a
+ * sum, a maximum or the histogram, so tv_mean = sum_tv / (leaves - nonfinite - empty).  Verified batches of cattus_hip_eval and of the
+ * leaf server (submit / wait / apply) carry no legal moves: they count in batches_without_legal and feed the value part alone.  The value
+ * part runs over every verified leaf of both paths whose two values are finite: sum_dvalue = sum |value - value_ref|.
+ * The asynchronous device entry points, cattus_hip_eval_device and cattus_hip_eval_device_lane, still do NOT verify and feed nothing.
+ *
+ * Cost: two HBM-trivial launches and 32 bytes per leaf of device-to-host copy behind a batch that already pays for an f32 pass; nothing
+ * for a batch that is not verified.  What the caller gets back is bit for bit what it gets without verification, and cattus_verify_stats
+ * and cattus_stats hold what they held.
+ *
+ * A dtype f32 evaluator and a SimpleTwoHeadedModel are CATTUS_E_UNSUPPORTED, as for cattus_hip_verify. */
+typedef struct cattus_prior_stats {
+    uint32_t struct_size; /* in: sizeof(cattus_prior_stats) */
+    uint32_t reserved;
+    uint64_t batches;               /* verified batches that came with legal moves */
+    uint64_t batches_without_legal; /* verified batches that did not: value part only */
+    uint64_t leaves;                /* leaves of `batches`, nonfinite and empty ones included */
+    uint64_t top1_flips;            /* leaves whose favourite move differs from the exact network's */
+    uint64_t nonfinite, empty;
+    double sum_tv, sum_regret;
+    float max_tv, max_regret;
+    uint64_t tv_hist[8];            /* upper edges 1e-7, 1e-6, .., 1e-1, +inf: a leaf is in the first bucket whose edge exceeds its tv */
+    uint64_t value_leaves;          /* verified leaves of both paths with two finite values */
+    double sum_dvalue;
+} cattus_prior_stats;
+int cattus_hip_verify_prior_stats(cattus_eval* e, cattus_prior_stats* out);
+/* The leaf that holds max_tv -- the first one compared, then every strictly larger one -- as it was given to the evaluator: its planes
+ * [planes][plane_words], its *legal_count = min(legal_count, legal_stride) legal moves into legal_idx[cap], and both favourites as positions in
+ * that list (*top this evaluator's, *top_ref the exact network's).  CATTUS_E_STATE before any leaf was compared, CATTUS_E_INVALID when
+ * cap is smaller than the leaf's legal count.  (cattus_hip_compare_priors() in cattus_hip_diag.h runs the comparison kernel alone.) */
+int cattus_hip_verify_worst_prior(cattus_eval* e, uint64_t* planes, uint16_t* legal_idx, uint32_t cap, uint32_t* legal_count, uint32_t* top,
+                                  uint32_t* top_ref);
+
 /* Layer-level observation.  leaves_outside > 0 or saturated > 0 says that this evaluator left the exact network somewhere; these two calls
  * say where.  A ConvNetV1 evaluator has P = 1 + 2 * blocks + 1 points:
  *   point 0        the stem ConvBlock's output (the residual stream), `filters` channels

@@ -67,6 +67,16 @@ int cattus_hip_stem_input(const cattus_eval* e, uint32_t* channels, uint32_t* pa
 int cattus_hip_compare_outputs(int device, const float* policy_a, const float* policy_b, const float* value_a, const float* value_b,
                                uint32_t n, uint32_t moves, void* records /* [n][16 bytes] */);
 
+/* The prior comparison kernel of cattus_hip_verify_prior_stats (cattus_hip.h) on host arrays.  probs_a / probs_b: [n][L] legal-move softmax
+ * rows, b the reference side; legal_count: [n] (a count above L is compared over L entries and flagged); value_a / value_b: [n];
+ * records: n x 32 bytes, per leaf
+ *   f32 tv, u32 top_a, u32 top_b, f32 regret = probs_b[top_b] - probs_b[top_a], f32 max |a - b|, u32 the lowest k that holds it,
+ *   u16 count = min(legal_count, L), u16 flags, f32 |value_a - value_b| (a NaN as 0x7fc00000)
+ *   flags: bit 0 a non-finite probability (tv and regret are then 0x7fc00000), bit 1 count == 0, bit 2 legal_count > L, bit 3 a non-finite value
+ * The same inputs give the same bytes on every run.  n >= 1, 1 <= L <= 1024. */
+int cattus_hip_compare_priors(int device, const float* probs_a, const float* probs_b, const uint16_t* legal_count, uint32_t n, uint32_t L,
+                              const float* value_a, const float* value_b, void* records /* [n][32 bytes] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,8 @@ the comparison sees the run-to-run spread.  The first `off` figures are taken be
     python scripts/verify_cost.py                 this tree
     python scripts/verify_cost.py --lib PATH      the same `off` loop on another build of the library (a commit without the entry
                                                   points, say), through nothing but the calls that build has
+    python scripts/verify_cost.py --mode eval_legal   the same table through cattus_hip_eval_legal (a seeded legal list of 20..40 moves per
+                                                  leaf, stride 64): verified batches then also compare the priors (cattus_hip_verify_prior_stats)
 """
 import argparse
 import ctypes as C
@@ -25,6 +27,7 @@ from cattus_amd.evaluator import EvalConfig, LIB_PATH  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--lib", default=str(LIB_PATH))
 ap.add_argument("--calls", type=int, default=200)
+ap.add_argument("--mode", choices=["eval", "eval_legal"], default="eval")
 ap.add_argument("--off-only", action="store_true", help="the `off` figures alone (four of them)")
 ap.add_argument("--out")
 ap.add_argument("--commit", help="what to write as the commit (default: git rev-parse HEAD)")
@@ -58,12 +61,23 @@ h_planes, h_policy, h_value = (L.cattus_hip_host_alloc(b) for b in (planes.nbyte
 C.memmove(h_planes, planes.ctypes.data, planes.nbytes)
 
 
+if args.mode == "eval_legal":
+    L.cattus_hip_eval_legal.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp]
+    rng = np.random.default_rng(1)
+    legal_idx = np.stack([rng.permutation(d.moves)[:64] for _ in range(n)]).astype(np.uint16)
+    legal_cnt = rng.integers(20, 41, size=n).astype(np.uint16)
+    h_probs = L.cattus_hip_host_alloc(n * 64 * 4)
+    one_call = lambda: L.cattus_hip_eval_legal(h, h_planes, n, legal_idx.ctypes.data, legal_cnt.ctypes.data, 64, h_probs, h_value)
+else:
+    one_call = lambda: L.cattus_hip_eval(h, h_planes, n, h_policy, h_value)
+
+
 def ms_per_call(calls):
     for _ in range(20):
-        check(L.cattus_hip_eval(h, h_planes, n, h_policy, h_value))
+        check(one_call())
     t0 = time.perf_counter()
     for _ in range(calls):
-        check(L.cattus_hip_eval(h, h_planes, n, h_policy, h_value))
+        check(one_call())
     return (time.perf_counter() - t0) / calls * 1e3
 
 
@@ -79,7 +93,7 @@ if not commit:
     except OSError:
         commit = "unknown"
 lines = ["command: python scripts/verify_cost.py " + " ".join(sys.argv[1:]), "library: " + args.lib, "commit: " + commit,
-         "chess 20x256, f16x2, batch %d, %d blocking cattus_hip_eval calls per figure from page-locked buffers, 20 warm-up calls each" % (n, args.calls),
+         "chess 20x256, f16x2, batch %d, %d blocking cattus_hip_%s calls per figure from page-locked buffers, 20 warm-up calls each" % (n, args.calls, args.mode),
          "every  ms_per_batch   (in the order measured)"]
 lines += ["%-6s %.4f" % r for r in rows]
 by = {}
