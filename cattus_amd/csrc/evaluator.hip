@@ -264,6 +264,14 @@ struct ServerBatch {
     std::vector<uint64_t> planes;
     std::vector<float> policy, value;
     std::vector<uint8_t> taken;  // per slot: its ticket has been waited for
+    // cattus_hip_submit_legal's leaves (legal_span.h): their lists back to back, the offset table as far as it is closed, and per slot whether it
+    // came with a list (slots behind the last one that did are plain).  All three stay empty in a batch of plain leaves.
+    std::vector<uint16_t> legal_idx;
+    std::vector<uint32_t> legal_off;
+    std::vector<uint8_t> kind;
+    uint32_t legal_leaves = 0;
+    std::vector<float> probs;  // [legal_off[count]], the legal leaves' softmax rows at their lists' places
+    bool is_legal(uint32_t slot) const { return slot < kind.size() && kind[slot]; }
 };
 
 constexpr int NLANES = CATTUS_HIP_LANES;
@@ -274,6 +282,11 @@ struct Lane {
     DevBuf d_planes, x0, a, t, y, hv, h1, d_policy, d_value;
     DevBuf d_legal_idx, d_legal_cnt, d_probs;  // legal-move softmax operands, allocated on first use
     uint32_t legal_stride = 0;
+    // the leaf server's ragged batches (legal_span.h), allocated for every lane at the first cattus_hip_submit_legal and sized for max_batch lists of
+    // 1024: the lists, the offset table [max_batch + 1] and the probabilities on the device and in page-locked memory; rag_probs_ref, the shadow's
+    // rows of a verified batch, on the lane's first such batch
+    DevBuf rag_idx, rag_off, rag_probs, rag_probs_ref;
+    PinnedBuf h_rag_idx, h_rag_off, h_rag_probs;
     // cattus_hip_stream_range, allocated on first use: the range kernel's workgroup partials, and the per-channel accumulators
     // [fpad sums of squares (double) | fpad maxima (float)] that collect over a call's tensors and chunks, ordered by `stream`
     DevBuf range_part_sq, range_part_max, range_acc;
@@ -410,6 +423,8 @@ struct cattus_eval {
     std::deque<std::unique_ptr<ServerBatch>> batches;  // oldest first; back() is collecting unless sealed
     uint64_t next_seq = 1;
     bool flush_req = false, stop = false;
+    std::mutex ragged_mu;  // the one-time allocation of the lanes' ragged buffers
+    std::atomic<bool> ragged_ready{false};
     std::thread servers[NLANES];  // one per lane: two sealed batches can be on the device together
 
     ~cattus_eval() {
@@ -951,6 +966,12 @@ struct LegalArgs {
     const uint16_t* cnt;  // [n]
     uint32_t stride;
     float* probs;  // [n][stride]
+    // The ragged form, a batch of the leaf server (legal_span.h): off [n + 1] is set, idx and probs hold off[n] entries back to back, cnt and stride
+    // are not read.  kind [n]: 0 marks a plain leaf (an empty span that is no leaf of the prior statistics); logits: some leaf is plain, so the
+    // logits come back too, into `policy`.
+    const uint32_t* off = nullptr;
+    const uint8_t* kind = nullptr;
+    bool logits = false;
 };
 
 // A lane for one blocking call, locked: a free one if there is one, else queue on one of them in turn.
@@ -1003,10 +1024,13 @@ void fold_priors(cattus_eval* e, const VerifyRecord* rec, uint32_t n, const uint
     }
     s.batches += 1;
     for (uint32_t i = 0; i < n; i++) {
+        // a ragged batch (the leaf server's) folds its leaves in slot order with their own lists; its plain leaves fed the value part above
+        if (lg->off && !lg->kind[i]) continue;
         if (!prior_fold(s, prior[i])) continue;
         cattus_eval::WorstPrior& w = e->worst_prior;
         w.planes.assign(planes + i * words, planes + (i + 1) * words);
-        w.legal.assign(lg->idx + (size_t)i * lg->stride, lg->idx + (size_t)i * lg->stride + prior[i].count);
+        const uint16_t* list = lg->idx + (lg->off ? (size_t)legal_span(lg->off, i).begin : (size_t)i * lg->stride);
+        w.legal.assign(list, list + prior[i].count);
         w.top = prior[i].top_a, w.top_ref = prior[i].top_b;
     }
 }
@@ -1026,8 +1050,18 @@ int eval_host(cattus_eval* e, const uint64_t* planes, uint32_t n, float* policy,
     const size_t pbytes = (size_t)n * d.planes * e->cfg.plane_words * 8;
     // Buffers obtained from cattus_hip_host_alloc are page-locked: DMA straight from / into them.
     // Anything else goes through the evaluator's own pinned staging buffers.
-    const bool direct = is_pinned(planes) && (lg || is_pinned(policy)) && is_pinned(value);
-    if (lg && (L.legal_stride < lg->stride || !L.d_probs.p)) {
+    const bool ragged = lg && lg->off, logits_out = !lg || lg->logits;
+    const bool direct = is_pinned(planes) && (!logits_out || is_pinned(policy)) && is_pinned(value);
+    const uint32_t rag_total = ragged ? lg->off[n] : 0;
+    if (ragged) {
+        // lists and offsets through the lane's page-locked staging, whatever the caller's memory is (the server's batches live in vectors)
+        if (!L.rag_idx.p) return fail(CATTUS_E_STATE, "ragged batch before the lanes' ragged buffers exist");
+        if (rag_total) memcpy(L.h_rag_idx.p, lg->idx, (size_t)rag_total * 2);
+        memcpy(L.h_rag_off.p, lg->off, ((size_t)n + 1) * 4);
+        if (verify && !L.rag_probs_ref.p)
+            if (int arc = L.rag_probs_ref.alloc((size_t)e->cfg.max_batch * LEGAL_CAP * 4)) return arc;
+    }
+    if (lg && !ragged && (L.legal_stride < lg->stride || !L.d_probs.p)) {
         const size_t B = e->cfg.max_batch;
         int arc;
         if ((arc = L.d_legal_idx.alloc(B * lg->stride * 2)) || (arc = L.d_legal_cnt.alloc(B * 2)) ||
@@ -1035,7 +1069,7 @@ int eval_host(cattus_eval* e, const uint64_t* planes, uint32_t n, float* policy,
             return arc;
         L.legal_stride = lg->stride;
     }
-    if (lg && verify && (L.prior_stride < lg->stride || !L.d_probs_ref.p)) {
+    if (lg && !ragged && verify && (L.prior_stride < lg->stride || !L.d_probs_ref.p)) {
         if (int arc = L.d_probs_ref.alloc((size_t)e->cfg.max_batch * lg->stride * 4)) return arc;
         L.prior_stride = lg->stride;
     }
@@ -1046,7 +1080,24 @@ int eval_host(cattus_eval* e, const uint64_t* planes, uint32_t n, float* policy,
     }
     HIP_TRY(hipMemcpyAsync(L.d_planes.p, src_planes, pbytes, hipMemcpyHostToDevice, L.stream));
     auto copy_out = [&]() -> int {
-        if (lg) {
+        if (ragged) {
+            // the leaf server's batch: the lists go up, the ragged softmax runs on the logits where they are, and only the probabilities (and the
+            // values, below) come back -- plus the logits where some leaf of the batch is a plain one
+            const uint32_t* d_off = L.rag_off.as<uint32_t>();
+            HIP_TRY(hipMemcpyAsync(L.rag_off.p, L.h_rag_off.p, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, L.stream));
+            if (rag_total) HIP_TRY(hipMemcpyAsync(L.rag_idx.p, L.h_rag_idx.p, (size_t)rag_total * 2, hipMemcpyHostToDevice, L.stream));
+            launch_legal_softmax_ragged(L.d_policy.as<float>(), d.moves, L.rag_idx.as<uint16_t>(), d_off, n, rag_total, L.rag_probs.as<float>(), L.stream);
+            if (verify) {
+                // as below: the shadow's logits through the same softmax with the same lists, the two sets of rows compared span by span
+                Lane& SL = e->shadow->lanes[&L - e->lanes];
+                launch_legal_softmax_ragged(SL.d_policy.as<float>(), d.moves, L.rag_idx.as<uint16_t>(), d_off, n, rag_total, L.rag_probs_ref.as<float>(), L.stream);
+                launch_verify_priors(L.rag_probs.as<float>(), L.rag_probs_ref.as<float>(), nullptr, L.d_value.as<float>(), SL.d_value.as<float>(), n, 0,
+                                     L.d_prior.as<PriorRecord>(), L.stream, d_off);
+                HIP_TRY(hipMemcpyAsync(L.h_prior.p, L.d_prior.p, (size_t)n * sizeof(PriorRecord), hipMemcpyDeviceToHost, L.stream));
+            }
+            if (rag_total) HIP_TRY(hipMemcpyAsync(L.h_rag_probs.p, L.rag_probs.p, (size_t)rag_total * 4, hipMemcpyDeviceToHost, L.stream));
+            if (logits_out) HIP_TRY(hipMemcpyAsync(direct ? (void*)policy : L.h_policy.p, L.d_policy.p, (size_t)n * d.moves * 4, hipMemcpyDeviceToHost, L.stream));
+        } else if (lg) {
             HIP_TRY(hipMemcpyAsync(L.d_legal_idx.p, lg->idx, (size_t)n * lg->stride * 2, hipMemcpyHostToDevice, L.stream));
             HIP_TRY(hipMemcpyAsync(L.d_legal_cnt.p, lg->cnt, (size_t)n * 2, hipMemcpyHostToDevice, L.stream));
             if (launch_legal_softmax(L.d_policy.as<float>(), d.moves, L.d_legal_idx.as<uint16_t>(), L.d_legal_cnt.as<uint16_t>(),
@@ -1099,9 +1150,10 @@ int eval_host(cattus_eval* e, const uint64_t* planes, uint32_t n, float* policy,
     if (rc) return rc;
     if (take_tower_give_up(e, L) && (rc = run_batch())) return rc;  // this batch again, from the planes, on the per-layer launches
     if (!direct) {
-        if (!lg) memcpy(policy, L.h_policy.p, (size_t)n * d.moves * 4);
+        if (logits_out) memcpy(policy, L.h_policy.p, (size_t)n * d.moves * 4);
         memcpy(value, L.h_value.p, (size_t)n * 4);
     }
+    if (rag_total) memcpy(lg->probs, L.h_rag_probs.p, (size_t)rag_total * 4);
     if (verify) {
         fold_verified(e, L.h_verify.as<VerifyRecord>(), n, static_cast<const uint64_t*>(src_planes));
         fold_priors(e, L.h_verify.as<VerifyRecord>(), n, static_cast<const uint64_t*>(src_planes), L.h_prior.as<PriorRecord>(), lg);
@@ -1150,11 +1202,20 @@ void server_loop(cattus_eval* e) {
         }
         run->running = true;
         const uint32_t n = run->count;
-        run->policy.resize((size_t)n * e->d.moves);
+        // a batch with lists runs the ragged softmax on the device; where all its leaves carry one, no logits come back at all
+        const bool ragged = run->legal_leaves > 0, logits = run->legal_leaves < n;
+        if (logits) run->policy.resize((size_t)n * e->d.moves);
         run->value.resize(n);
         run->taken.assign(n, 0);
+        LegalArgs lg{};
+        if (ragged) {
+            legal_close(run->legal_off, n);
+            run->kind.resize(n, 0);
+            run->probs.resize(run->legal_off[n]);
+            lg.idx = run->legal_idx.data(), lg.probs = run->probs.data(), lg.off = run->legal_off.data(), lg.kind = run->kind.data(), lg.logits = logits;
+        }
         lk.unlock();
-        const int rc = eval_host(e, run->planes.data(), n, run->policy.data(), run->value.data());
+        const int rc = eval_host(e, run->planes.data(), n, logits ? run->policy.data() : nullptr, run->value.data(), ragged ? &lg : nullptr);
         std::string err = rc ? g_last_error : std::string();
         lk.lock();
         run->status = rc;
@@ -1548,8 +1609,9 @@ CATTUS_API int cattus_hip_lane_stream(cattus_eval* e, uint32_t lane, void** stre
     return CATTUS_OK;
 }
 
-CATTUS_API int cattus_hip_submit(cattus_eval* e, const uint64_t* planes_one, uint64_t* ticket) {
-    if (!e || !planes_one || !ticket) return fail(CATTUS_E_INVALID, "NULL argument");
+// One leaf into the collecting batch.  list: NULL for cattus_hip_submit, else the leaf's legal_count policy indices (already checked), appended to
+// the batch's ragged table (legal_span.h).
+static int submit_leaf(cattus_eval* e, const uint64_t* planes_one, const uint16_t* list, uint32_t legal_count, uint64_t* ticket) {
     const size_t words = (size_t)e->d.planes * e->cfg.plane_words;
     std::unique_lock<std::mutex> lk(e->srv_mu);
     if (e->stop) return fail(CATTUS_E_STATE, "evaluator is shutting down");
@@ -1559,6 +1621,12 @@ CATTUS_API int cattus_hip_submit(cattus_eval* e, const uint64_t* planes_one, uin
     const uint32_t slot = cur->count++;
     if (slot == 0) cur->t0 = std::chrono::steady_clock::now();
     memcpy(cur->planes.data() + slot * words, planes_one, words * 8);
+    if (list) {
+        legal_append(cur->legal_idx, cur->legal_off, slot, list, legal_count);
+        cur->kind.resize(slot, 0);
+        cur->kind.push_back(1);
+        cur->legal_leaves += 1;
+    }
     *ticket = (cur->seq << 32) | slot;
     const bool full = cur->count == e->cfg.max_batch;
     if (full) {
@@ -1570,8 +1638,48 @@ CATTUS_API int cattus_hip_submit(cattus_eval* e, const uint64_t* planes_one, uin
     return CATTUS_OK;
 }
 
-CATTUS_API int cattus_hip_wait(cattus_eval* e, uint64_t ticket, float* policy, float* value) {
-    if (!e || !policy || !value) return fail(CATTUS_E_INVALID, "NULL argument");
+CATTUS_API int cattus_hip_submit(cattus_eval* e, const uint64_t* planes_one, uint64_t* ticket) {
+    if (!e || !planes_one || !ticket) return fail(CATTUS_E_INVALID, "NULL argument");
+    return submit_leaf(e, planes_one, nullptr, 0, ticket);
+}
+
+// The lanes' ragged buffers (Lane::rag_*), once per evaluator, at its first cattus_hip_submit_legal: each lane is taken in turn, so the call waits
+// for the batch in flight on it.  An evaluator that never submits a list allocates none of this.
+static int ragged_buffers(cattus_eval* e) {
+    if (e->ragged_ready.load(std::memory_order_acquire)) return CATTUS_OK;
+    std::lock_guard<std::mutex> once(e->ragged_mu);
+    if (e->ragged_ready.load(std::memory_order_relaxed)) return CATTUS_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t B = e->cfg.max_batch, entries = B * LEGAL_CAP;
+    for (Lane& L : e->lanes) {
+        std::lock_guard<std::mutex> lk(L.mu);
+        int rc = CATTUS_OK;
+        if ((!L.rag_idx.p && (rc = L.rag_idx.alloc(entries * 2))) || (!L.rag_off.p && (rc = L.rag_off.alloc((B + 1) * 4))) ||
+            (!L.rag_probs.p && (rc = L.rag_probs.alloc(entries * 4))) || (!L.h_rag_idx.p && (rc = L.h_rag_idx.alloc(entries * 2))) ||
+            (!L.h_rag_off.p && (rc = L.h_rag_off.alloc((B + 1) * 4))) || (!L.h_rag_probs.p && (rc = L.h_rag_probs.alloc(entries * 4))))
+            return rc;
+    }
+    e->ragged_ready.store(true, std::memory_order_release);
+    return CATTUS_OK;
+}
+
+static const char* legal_fault_text(LegalFault f) {
+    return f == LEGAL_TOO_LONG ? "more than 1024 legal moves" : f == LEGAL_BAD_INDEX ? "a policy index outside the network's moves" : "offsets do not ascend from 0";
+}
+
+CATTUS_API int cattus_hip_submit_legal(cattus_eval* e, const uint64_t* planes_one, const uint16_t* legal_idx, uint32_t legal_count, uint64_t* ticket) {
+    if (!e || !planes_one || !ticket || (!legal_idx && legal_count)) return fail(CATTUS_E_INVALID, "NULL argument");
+    uint32_t at = 0;
+    if (const LegalFault f = legal_list_check(legal_idx, legal_count, e->d.moves, &at))
+        return fail(CATTUS_E_INVALID, "legal list of %u entries: %s (position %u, moves %u)", legal_count, legal_fault_text(f), at, e->d.moves);
+    if (int rc = ragged_buffers(e)) return rc;
+    static const uint16_t none = 0;  // a list of no entries still is one: the leaf is a legal leaf with an empty span
+    return submit_leaf(e, planes_one, legal_idx ? legal_idx : &none, legal_count, ticket);
+}
+
+// cattus_hip_wait (legal == false: policy receives the logits) and cattus_hip_wait_legal (legal == true: probs receives the leaf's legal_count
+// probabilities).  A ticket of the other kind is refused before anything is waited for or marked: the right call can still claim it.
+static int wait_leaf(cattus_eval* e, uint64_t ticket, bool legal, float* out, float* value) {
     const uint64_t seq = ticket >> 32;
     const uint32_t slot = (uint32_t)ticket;
     std::unique_lock<std::mutex> lk(e->srv_mu);
@@ -1583,15 +1691,25 @@ CATTUS_API int cattus_hip_wait(cattus_eval* e, uint64_t ticket, float* policy, f
                 break;
             }
         if (!b || slot >= b->count) return fail(CATTUS_E_STATE, "unknown or already collected ticket %llu", (unsigned long long)ticket);
+        if (b->is_legal(slot) != legal)
+            return fail(CATTUS_E_INVALID, "ticket %llu is a %s: claim it with %s", (unsigned long long)ticket,
+                        legal ? "cattus_hip_submit ticket" : "cattus_hip_submit_legal ticket", legal ? "cattus_hip_wait" : "cattus_hip_wait_legal");
         if (b->done) {
             // a ticket is single-use whether its batch succeeded or not: the last waiter through erases the batch
             if (slot >= b->taken.size() || b->taken[slot]) return fail(CATTUS_E_STATE, "ticket %llu was already collected", (unsigned long long)ticket);
+            if (legal && !out && b->status == CATTUS_OK && legal_span(b->legal_off.data(), slot).count)
+                return fail(CATTUS_E_INVALID, "NULL probs for a leaf with legal moves");
             b->taken[slot] = 1;
             const int status = b->status;
             if (status != CATTUS_OK) {
                 g_last_error = b->error;
             } else {
-                memcpy(policy, b->policy.data() + (size_t)slot * e->d.moves, (size_t)e->d.moves * 4);
+                if (legal) {
+                    const LegalSpan sp = legal_span(b->legal_off.data(), slot);
+                    if (sp.count) memcpy(out, b->probs.data() + sp.begin, (size_t)sp.count * 4);
+                } else {
+                    memcpy(out, b->policy.data() + (size_t)slot * e->d.moves, (size_t)e->d.moves * 4);
+                }
                 *value = b->value[slot];
             }
             if (++b->collected == b->count) {
@@ -1606,6 +1724,43 @@ CATTUS_API int cattus_hip_wait(cattus_eval* e, uint64_t ticket, float* policy, f
         if (e->stop) return fail(CATTUS_E_STATE, "evaluator is shutting down");
         e->done_cv.wait(lk);
     }
+}
+
+CATTUS_API int cattus_hip_wait(cattus_eval* e, uint64_t ticket, float* policy, float* value) {
+    if (!e || !policy || !value) return fail(CATTUS_E_INVALID, "NULL argument");
+    return wait_leaf(e, ticket, false, policy, value);
+}
+
+CATTUS_API int cattus_hip_wait_legal(cattus_eval* e, uint64_t ticket, float* probs, float* value) {
+    if (!e || !value) return fail(CATTUS_E_INVALID, "NULL argument");  // probs may be NULL for a leaf without a legal move
+    return wait_leaf(e, ticket, true, probs, value);
+}
+
+CATTUS_API int cattus_hip_apply_legal(cattus_eval* e, const uint64_t* planes, uint32_t n, const uint16_t* legal_idx, const uint32_t* legal_off, float* probs,
+                                      float* value) {
+    if (!e || !planes || !legal_off || !value) return fail(CATTUS_E_INVALID, "NULL argument");
+    // the whole table is checked before the first leaf is queued: a refused call leaves nothing behind
+    uint32_t at = 0;
+    if (const LegalFault f = legal_offsets_check(legal_off, n, &at)) return fail(CATTUS_E_INVALID, "legal_off: %s (leaf %u)", legal_fault_text(f), at);
+    const uint32_t total = legal_off[n];
+    if (total && (!legal_idx || !probs)) return fail(CATTUS_E_INVALID, "NULL argument");
+    for (uint32_t k = 0; k < total; k++)
+        if (legal_idx[k] >= e->d.moves)
+            return fail(CATTUS_E_INVALID, "leaf %u: policy index %u >= %u", legal_owner(legal_off, n, k), legal_idx[k], e->d.moves);
+    const size_t words = (size_t)e->d.planes * e->cfg.plane_words;
+    std::vector<uint64_t> tickets(n);
+    int rc = CATTUS_OK;
+    uint32_t submitted = 0;
+    for (; submitted < n; submitted++) {
+        const LegalSpan sp = legal_span(legal_off, submitted);
+        if ((rc = cattus_hip_submit_legal(e, planes + submitted * words, legal_idx + sp.begin, sp.count, &tickets[submitted]))) break;
+    }
+    // as cattus_hip_apply: every submitted ticket is collected, also after a failure
+    for (uint32_t i = 0; i < submitted; i++) {
+        const int wrc = cattus_hip_wait_legal(e, tickets[i], probs + legal_off[i], value + i);
+        if (wrc && !rc) rc = wrc;
+    }
+    return rc;
 }
 
 CATTUS_API int cattus_hip_apply(cattus_eval* e, const uint64_t* planes, uint32_t n, float* policy, float* value) {

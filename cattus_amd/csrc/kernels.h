@@ -6,6 +6,7 @@
 #include "frag_index.h"  // split_frag_index, wino_frag_index, WINO_RING_STAGES
 #include "verify_rule.h"  // VerifyRecord and the rule behind it
 #include "prior_rule.h"   // PriorRecord and the rule behind it
+#include "legal_span.h"   // the ragged layout of the leaf server's legal-move lists
 #include "tap_layout.h"   // TapSource, TraceRecord: where a point's activations live, the rule of a trace record
 
 namespace cattus {
@@ -135,8 +136,10 @@ void launch_verify_outputs(const float* policy_a, const float* policy_b, const f
 
 // probs_a / probs_b: [n][L] legal-move softmax rows of the evaluator and of its shadow (launch_legal_softmax on either's logits), cnt: [n]
 // legal counts, value_a / value_b: [n]; records: [n], one prior_rule.h record per leaf.  The same inputs give the same bytes on every run.
+// row_off: NULL, or the offset table [n + 1] of a ragged batch (legal_span.h): leaf i's two rows then start at row_off[i] and are as long as
+// its list, and cnt / L are not read.
 void launch_verify_priors(const float* probs_a, const float* probs_b, const uint16_t* cnt, const float* value_a, const float* value_b, uint32_t n,
-                          uint32_t L, PriorRecord* records, hipStream_t st);
+                          uint32_t L, PriorRecord* records, hipStream_t st, const uint32_t* row_off = nullptr);
 
 // ---- observation: one point of the network (cattus_hip_tap, cattus_hip_trace; tap_layout.h has the layouts and the record) ----
 // src: the tensor as the evaluator holds it (TapSource), shifts: NULL, or per live channel the exponent t the tensor carries it at (device,
@@ -262,6 +265,10 @@ void launch_value_fc2_tanh(const float* h1, const float* w2, const float* b2, ui
 // Softmax over each leaf's legal moves (net/mod.rs:100-119): idx [b][L] policy indices, cnt [b] <= L, probs [b][L].
 int launch_legal_softmax(const float* policy, uint32_t M, const uint16_t* idx, const uint16_t* cnt, uint32_t L, uint32_t b,
                          float* probs, hipStream_t st);
+// The same softmax on a ragged batch (legal_span.h): idx / probs [total] back to back, off [n + 1], total == off[n]; every list <= 1024
+// entries (the host checks).  The same leaf and list give launch_legal_softmax's bits.  total == 0 launches nothing.
+void launch_legal_softmax_ragged(const float* policy, uint32_t M, const uint16_t* idx, const uint32_t* off, uint32_t n, uint32_t total, float* probs,
+                                 hipStream_t st);
 void launch_policy_fc(const float* hv, uint32_t hv_stride, uint32_t off, const float* wpt, const float* bp, uint32_t b,
                       uint32_t K, uint32_t M, float* policy, hipStream_t st);
 // One dense layer of SimpleTwoHeadedModel (training/cattus_train/net_utils.py:92-121), f32, the term order of every

@@ -17,7 +17,9 @@
 //       verify_outputs                                      verification: two runtimes' logits and values of a batch against the reference's
 //                                                           cross-runtime bar, one record per leaf (HBM-trivial, verified batches only)
 //       verify_priors                                       the same batch's legal-move priors against the shadow's: total variation, favourites,
-//                                                           regret, one record per leaf (HBM-trivial, verified eval_legal batches only)
+//                                                           regret, one record per leaf (HBM-trivial, verified batches with legal moves only)
+//       legal_softmax, legal_softmax_ragged                 calc_moves_probs on the device: cattus_hip_eval_legal's padded rows, and the leaf
+//                                                           server's ragged batches (legal_span.h); the same arithmetic, the same bits
 //       tap_rows, tap_gather, trace_compare                 observation: one point's activations as f32 NCHW, or against the f32 shadow's,
 //                                                           one record per leaf (HBM-trivial, cattus_hip_tap / cattus_hip_trace only)
 //
@@ -2396,6 +2398,53 @@ int launch_legal_softmax(const float* policy, uint32_t M, const uint16_t* idx, c
     return 0;
 }
 
+// The same softmax on the leaf server's ragged layout (legal_span.h): leaf i owns idx / probs [off[i], off[i + 1]).  One wave per leaf,
+// four leaves per workgroup, a 1024-float LDS row per wave.  A span starts wherever the one before it ended -- 2-byte alignment for idx,
+// 4-byte for probs -- so these are plain 2- and 4-byte loads and stores (verify_priors_kernel's choice, at the same trivial traffic).
+// The arithmetic is legal_softmax_kernel's, operation for operation: max = fold(f32::MIN, max), exp_nonpos(v - max), the sum taken by
+// one lane in move order, e / s -- the same leaf and list give the bits cattus_hip_eval_legal gives.  A leaf with an empty span (no legal
+// move, or a plain leaf of a mixed batch) and the waves behind the last leaf write nothing; they still take both barriers, which every
+// thread of the workgroup reaches.  HBM-trivial and off the tower's critical path: nobody has timed it.
+__global__ void __launch_bounds__(256) legal_softmax_ragged_kernel(const float* __restrict__ policy, uint32_t M, const uint16_t* __restrict__ idx,
+                                                                   const uint32_t* __restrict__ off, uint32_t n, float* __restrict__ probs) {
+    __shared__ float es_all[4][LEGAL_CAP];
+    __shared__ float total[4];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, leaf = blockIdx.x * 4 + wave;
+    LegalSpan sp{0, 0};
+    if (leaf < n) sp = legal_span(off, leaf);
+    const uint32_t c = sp.count < LEGAL_CAP ? sp.count : LEGAL_CAP;  // the host refuses longer lists; the LDS row holds no more
+    float* es = es_all[wave];
+    const float* row = policy + (size_t)(leaf < n ? leaf : 0) * M;
+    const uint16_t* ix = idx + sp.begin;
+    float mx = -3.40282347e+38f;  // fold(f32::MIN, f32::max)
+    for (uint32_t i = lane; i < c; i += 64) {
+        const float v = row[ix[i]];
+        es[i] = v;
+        mx = v > mx ? v : mx;
+    }
+    for (int o = 32; o; o >>= 1) {
+        const float other = __shfl_xor(mx, o);
+        mx = other > mx ? other : mx;
+    }
+    for (uint32_t i = lane; i < c; i += 64) es[i] = exp_nonpos(es[i] - mx);
+    __syncthreads();
+    if (lane == 0) {
+        float s = 0.0f;
+        for (uint32_t i = 0; i < c; i++) s += es[i];
+        total[wave] = s;
+    }
+    __syncthreads();
+    const float s = total[wave];
+    float* out = probs + sp.begin;
+    for (uint32_t i = lane; i < c; i += 64) out[i] = es[i] / s;
+}
+
+void launch_legal_softmax_ragged(const float* policy, uint32_t M, const uint16_t* idx, const uint32_t* off, uint32_t n, uint32_t total, float* probs,
+                                 hipStream_t st) {
+    if (!n || !total) return;  // a grid of zero blocks is a HIP error, and nothing would be written anyway
+    hipLaunchKernelGGL(legal_softmax_ragged_kernel, dim3((n + 3) / 4), dim3(256), 0, st, policy, M, idx, off, n, probs);
+}
+
 // Block = 256 logits x 8 leaves; the 8 input rows are staged in LDS, every weight is loaded once
 // (coalesced along m) and used for 8 fmaf.
 constexpr int PFC_ROWS = 8;
@@ -2588,12 +2637,16 @@ void launch_verify_outputs(const float* policy_a, const float* policy_b, const f
 // largest difference combine order-free.  Lane 0 writes the 32-byte record; no atomics, the same bytes on every run.
 __global__ void __launch_bounds__(256) verify_priors_kernel(const float* __restrict__ pa, const float* __restrict__ pb, const uint16_t* __restrict__ cnt,
                                                             const float* __restrict__ value_a, const float* __restrict__ value_b, uint32_t n, uint32_t L,
-                                                            PriorRecord* __restrict__ records) {
+                                                            PriorRecord* __restrict__ records, const uint32_t* __restrict__ row_off) {
     const uint32_t lane = threadIdx.x & 63, leaf = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (leaf >= n) return;  // whole waves leave: nothing below synchronises across waves
-    const float* ra = pa + (size_t)leaf * L;
-    const float* rb = pb + (size_t)leaf * L;
-    const uint32_t count = cnt[leaf], c = count < L ? count : L;
+    // row_off (the leaf server's ragged batches, legal_span.h): leaf's two rows start at row_off[leaf] and are as long as its list, so cnt and
+    // L are not read; NULL: rows at leaf * L
+    if (row_off) L = legal_span(row_off, leaf).count;
+    const size_t at = row_off ? (size_t)row_off[leaf] : (size_t)leaf * L;
+    const float* ra = pa + at;
+    const float* rb = pb + at;
+    const uint32_t count = row_off ? L : cnt[leaf], c = count < L ? count : L;
     PriorPartial p;
     for (uint32_t k = lane; k < c; k += PRIOR_LANES) prior_take(p, ra[k], rb[k], k);
     double s = prior_lane_sum(ra, rb, c, lane);
@@ -2610,9 +2663,9 @@ __global__ void __launch_bounds__(256) verify_priors_kernel(const float* __restr
 }
 
 void launch_verify_priors(const float* pa, const float* pb, const uint16_t* cnt, const float* value_a, const float* value_b, uint32_t n, uint32_t L,
-                          PriorRecord* records, hipStream_t st) {
+                          PriorRecord* records, hipStream_t st, const uint32_t* row_off) {
     if (!n) return;
-    hipLaunchKernelGGL(verify_priors_kernel, dim3((n + 3) / 4), dim3(256), 0, st, pa, pb, cnt, value_a, value_b, n, L, records);
+    hipLaunchKernelGGL(verify_priors_kernel, dim3((n + 3) / 4), dim3(256), 0, st, pa, pb, cnt, value_a, value_b, n, L, records, row_off);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -40,6 +40,9 @@ ABI_SYMBOLS = [
     "cattus_hip_wait",
     "cattus_hip_flush",
     "cattus_hip_apply",
+    "cattus_hip_submit_legal",
+    "cattus_hip_wait_legal",
+    "cattus_hip_apply_legal",
     "cattus_hip_host_alloc",
     "cattus_hip_host_free",
     "cattus_hip_stats",
@@ -204,6 +207,9 @@ def load_library():
     L.cattus_hip_wait.argtypes = [vp, C.c_uint64, f32p, f32p]
     L.cattus_hip_flush.argtypes = [vp]
     L.cattus_hip_apply.argtypes = [vp, u64p, C.c_uint32, f32p, f32p]
+    L.cattus_hip_submit_legal.argtypes = [vp, u64p, u16p, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.cattus_hip_wait_legal.argtypes = [vp, C.c_uint64, f32p, f32p]
+    L.cattus_hip_apply_legal.argtypes = [vp, u64p, C.c_uint32, u16p, C.POINTER(C.c_uint32), f32p, f32p]
     L.cattus_hip_host_alloc.argtypes = [C.c_size_t]
     L.cattus_hip_host_alloc.restype = vp
     L.cattus_hip_host_free.argtypes = [vp]
@@ -326,6 +332,7 @@ class HipEvaluator:
         self.dtype = dtype
         self.device = device
         self._lib = load_library()
+        self._legal_counts: dict[int, int] = {}  # submit_legal ticket -> its list's length, until wait_legal
         if tower_form is None:
             legacy = os.environ.get("CATTUS_WINOGRAD")
             tower_form = "auto" if not legacy else ("winograd" if legacy[0] == "1" else "direct")
@@ -442,6 +449,56 @@ class HipEvaluator:
     def flush(self):
         _check(self._lib.cattus_hip_flush(self._h))
 
+    # the same with calc_moves_probs (net/mod.rs:100-119) on the device: a leaf's legal-move priors come back instead of its logits
+    def submit_legal(self, planes_one, legal_idx) -> int:
+        """One leaf with its legal moves' policy indices (uint16, at most 1024, each < moves; may be empty) -> ticket for ``wait_legal``."""
+        p = np.ascontiguousarray(planes_one, dtype=np.uint64).reshape(self.desc.planes, self.plane_words)
+        idx = np.ascontiguousarray(legal_idx, dtype=np.uint16).reshape(-1)
+        t = C.c_uint64()
+        _check(self._lib.cattus_hip_submit_legal(self._h, _u64(p), idx.ctypes.data_as(C.POINTER(C.c_uint16)), len(idx), C.byref(t)))
+        self._legal_counts[t.value] = len(idx)
+        return t.value
+
+    def wait_legal(self, ticket: int) -> tuple[np.ndarray, float]:
+        """(probs ``[legal_count of that submit]``, value) of a ``submit_legal`` ticket."""
+        count = self._legal_counts.get(ticket, 1024)  # a ticket that is not one of submit_legal's: the library refuses it
+        probs = np.empty((count,), dtype=np.float32)
+        value = C.c_float()
+        _check(self._lib.cattus_hip_wait_legal(self._h, ticket, _f32(probs), C.byref(value)))
+        self._legal_counts.pop(ticket, None)
+        return probs, value.value
+
+    def apply_legal(self, planes, legal_lists) -> tuple[list[np.ndarray], np.ndarray]:
+        """``submit_legal`` + ``wait_legal`` for n leaves, blocking (cattus_hip_apply_legal): planes uint64 ``[n, C, plane_words]`` and one
+        list of policy indices per leaf -> (one probs array per leaf, values ``[n]``)."""
+        planes = self._planes(planes)
+        n = planes.shape[0]
+        lists = [np.ascontiguousarray(l, dtype=np.uint16).reshape(-1) for l in legal_lists]
+        if len(lists) != n:
+            raise ValueError("apply_legal: one legal list per leaf")
+        off = np.zeros(n + 1, dtype=np.uint32)
+        np.cumsum([len(l) for l in lists], out=off[1:])
+        probs, value = self.apply_legal_ragged(planes, np.concatenate(lists) if lists else np.zeros(0, dtype=np.uint16), off)
+        return [probs[off[i] : off[i + 1]].copy() for i in range(n)], value
+
+    def apply_legal_ragged(self, planes, legal_idx, legal_off) -> tuple[np.ndarray, np.ndarray]:
+        """cattus_hip_apply_legal on its own layout: legal_idx uint16 ``[total]``, legal_off uint32 ``[n + 1]`` -> (probs ``[total]``, values ``[n]``)."""
+        planes = self._planes(planes)
+        n = planes.shape[0]
+        idx = np.ascontiguousarray(legal_idx, dtype=np.uint16).reshape(-1)
+        off = np.ascontiguousarray(legal_off, dtype=np.uint32).reshape(-1)
+        if len(off) != n + 1:
+            raise ValueError("apply_legal_ragged: legal_off must have n + 1 entries")
+        # a table the library will refuse may point past the list: both buffers cover whatever it names
+        total = len(idx)
+        need = max(total, int(off.max()), 1)
+        idx = np.concatenate([idx, np.zeros(need - len(idx), dtype=np.uint16)])
+        probs = np.zeros((need,), dtype=np.float32)
+        value = np.empty((n,), dtype=np.float32)
+        _check(self._lib.cattus_hip_apply_legal(self._h, _u64(planes), n, idx.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                                off.ctypes.data_as(C.POINTER(C.c_uint32)), _f32(probs), _f32(value)))
+        return probs[:total], value
+
     # -- introspection ----------------------------------------------------------------------
     def stats(self) -> dict:
         s = Stats()
@@ -471,7 +528,7 @@ class HipEvaluator:
         return out
 
     def verify_prior_stats(self) -> dict:
-        """The priors part of the sticky record (cattus_prior_stats): what the verified ``eval_legal`` batches' legal-move priors and every
+        """The priors part of the sticky record (cattus_prior_stats): what the legal-move priors of the verified ``eval_legal`` batches and ``submit_legal`` / ``apply_legal`` leaves and every
         verified batch's values differ by from the exact network's -- batches, batches_without_legal, leaves, top1_flips, nonfinite, empty,
         sum_tv, sum_regret, max_tv, max_regret, tv_hist (upper edges 1e-7 .. 1e-1, inf), value_leaves, sum_dvalue -- and derived from them
         tv_mean and regret_mean over the leaves that entered the sums and dvalue_mean over value_leaves (0.0 where there are none)."""

@@ -68,3 +68,24 @@ def random_ttt_planes(n: int, seed: int) -> np.ndarray:
                 x |= 1 << i
         out[b, :, 0] = [x, o, 511]
     return out
+
+
+def random_legal_lists(n: int, moves: int, lo: int, hi: int, seed: int) -> list[np.ndarray]:
+    """One seeded list of lo..hi distinct policy indices per leaf (uint16): stand-ins for the legal moves of n positions."""
+    rng = np.random.default_rng(seed)
+    return [rng.permutation(moves)[: int(rng.integers(lo, hi + 1))].astype(np.uint16) for _ in range(n)]
+
+
+def write_legal_leaves(path, planes: np.ndarray, lists) -> None:
+    """The leaves file integration/c/consumer_legal.c reads: u32 n, words per leaf, total, 0; u64 planes [n][words]; u32 off [n + 1];
+    u16 idx [total], leaf i's list at idx[off[i] : off[i + 1]] (the ragged layout of cattus_hip_apply_legal)."""
+    planes = np.ascontiguousarray(planes, dtype=np.uint64)
+    n = planes.shape[0]
+    if len(lists) != n:
+        raise ValueError("write_legal_leaves: one legal list per leaf")
+    off = np.zeros(n + 1, dtype=np.uint32)
+    np.cumsum([len(l) for l in lists], out=off[1:])
+    idx = np.concatenate([np.asarray(l, dtype=np.uint16) for l in lists]) if n else np.zeros(0, dtype=np.uint16)
+    with open(path, "wb") as f:
+        f.write(np.array([n, planes[0].size if n else 0, len(idx), 0], dtype=np.uint32).tobytes())
+        f.write(planes.tobytes() + off.tobytes() + idx.astype(np.uint16).tobytes())

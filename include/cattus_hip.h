@@ -176,6 +176,32 @@ int cattus_hip_flush(cattus_eval* e);
  * threads submit meanwhile; a batch runs when max_batch leaves are queued or flush_us have passed. */
 int cattus_hip_apply(cattus_eval* e, const uint64_t* planes, uint32_t n, float* policy, float* value);
 
+/* The leaf server with calc_moves_probs (engine/src/net/mod.rs:100-119) on the device: what a search thread of the reference does per
+ * leaf -- Batcher::apply (engine/src/util/batch.rs:49-177), then the softmax over the leaf's legal moves on the host -- as one call.  The
+ * logits stay in HBM; the leaf's probabilities come back in place of its M logits.
+ *
+ * Batcher::apply + calc_moves_probs per leaf.  legal_idx: legal_count policy indices (Move::to_nn_idx) in the order the caller wants the
+ * probabilities back; 0 <= legal_count <= 1024, every index < moves: anything else is CATTUS_E_INVALID, checked on the host at submit, and
+ * nothing is queued.  legal_count == 0 is valid: the value comes back and no probability is written (legal_idx and probs may be NULL).
+ *
+ * Leaves of cattus_hip_submit and cattus_hip_submit_legal share batches, their sealing (max_batch leaves, flush_us, cattus_hip_flush) and
+ * the lanes.  Inside a batch the lists lie back to back with one offset per leaf (a ragged layout: no stride to agree on); a batch whose
+ * leaves all carry a list copies no logits to the host, only its probabilities and values; a mixed batch copies the logits as well, for its
+ * plain leaves.  The arithmetic is cattus_hip_eval_legal's -- max = fold(f32::MIN, max), the evaluator's own exp, the sum in move order
+ *  -- so a leaf and its list give that call's bits, whatever batch they came in, and a host restatement reproduces them.
+ *
+ * A ticket is claimed by the call that matches its submit: cattus_hip_wait on a legal ticket and cattus_hip_wait_legal on a plain one are
+ * CATTUS_E_INVALID and leave the ticket claimable by the right call.  SimpleTwoHeadedModel evaluators are supported, as by cattus_hip_eval_legal.
+ * The first cattus_hip_submit_legal of an evaluator allocates the staging for max_batch lists of 1024 per lane (it waits for the batches in
+ * flight); an evaluator that never calls these entry points allocates nothing for them. */
+int cattus_hip_submit_legal(cattus_eval* e, const uint64_t* planes_one, const uint16_t* legal_idx, uint32_t legal_count, uint64_t* ticket);
+int cattus_hip_wait_legal(cattus_eval* e, uint64_t ticket, float* probs /* [legal_count of that submit] */, float* value);
+/* submit_legal + wait_legal for n leaves, blocking, through the server like cattus_hip_apply:
+ * legal_off [n + 1] ascending with legal_off[0] == 0; legal_idx and probs hold legal_off[n] entries back to back.  Offsets that do not start
+ * at 0 or descend, a list above 1024 and an index >= moves are CATTUS_E_INVALID, checked before the first leaf is queued. */
+int cattus_hip_apply_legal(cattus_eval* e, const uint64_t* planes, uint32_t n, const uint16_t* legal_idx, const uint32_t* legal_off,
+                           float* probs, float* value);
+
 /* Page-locked host memory.  cattus_hip_eval transfers directly from / into buffers allocated here
  * (no staging copy); any other host memory works too, through the evaluator's own staging buffers. */
 void* cattus_hip_host_alloc(size_t bytes);
@@ -238,9 +264,12 @@ int cattus_hip_verify_worst_planes(cattus_eval* e, uint64_t* planes /* [planes][
  *   regret  = pb[top_ref] - pb[top]: the prior mass the exact network's favourite loses; top / top_ref are the positions in the legal
  *             list of the largest pa / pb, the lowest on ties; exactly 0 when they agree, >= 0 otherwise
  * A leaf with a non-finite probability on either side is counted in `nonfinite`, one with legal_count == 0 in `empty`; neither enters a
- * sum, a maximum or the histogram, so tv_mean = sum_tv / (leaves - nonfinite - empty).  Verified batches of cattus_hip_eval and of the
- * leaf server (submit / wait / apply) carry no legal moves: they count in batches_without_legal and feed the value part alone.  The value
- * part runs over every verified leaf of both paths whose two values are finite: sum_dvalue = sum |value - value_ref|.
+ * sum, a maximum or the histogram, so tv_mean = sum_tv / (leaves - nonfinite - empty).  Verified batches of cattus_hip_eval carry no legal
+ * moves: they count in batches_without_legal and feed the value part alone.  A verified batch of the leaf server feeds it the same way as
+ * cattus_hip_eval_legal when at least one of its leaves came through cattus_hip_submit_legal / cattus_hip_apply_legal: those leaves are compared
+ * in slot order, each over its own list (c = its legal_count), and the batch's plain leaves (cattus_hip_submit / apply) feed the value part
+ * alone; a server batch of plain leaves only counts in batches_without_legal.  The value
+ * part runs over every verified leaf of all paths whose two values are finite: sum_dvalue = sum |value - value_ref|.
  * The asynchronous device entry points, cattus_hip_eval_device and cattus_hip_eval_device_lane, still do NOT verify and feed nothing.
  *
  * Cost: two HBM-trivial launches and 32 bytes per leaf of device-to-host copy behind a batch that already pays for an f32 pass; nothing
