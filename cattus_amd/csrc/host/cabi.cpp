@@ -53,14 +53,27 @@ SelfPlayConfig to_config(const cattus_sp_config* c, uint32_t games_num = 0) {
     cfg.eval_threads = c->eval_threads ? std::min(c->eval_threads, 256u) : 2;
     cfg.mcts.leaves_in_flight = std::max(1u, std::min(c->leaves_in_flight, 16u));
     cfg.max_game_plies = c->max_game_plies;
+    cfg.prefetch = c->prefetch;
+    cfg.prefetch_fill = c->prefetch_fill;
     if (c->game_list) cfg.game_list.assign(c->game_list, c->game_list + games_num);
     if (c->progress_path) cfg.progress_path = c->progress_path;
     return cfg;
 }
 
 // What TemperaturePolicy::scheduled asserts (mcts/mod.rs:463-476) plus the limits of the C struct; nullptr = ok.
-const char* config_error(const cattus_sp_config* c) {
-    if (!c || c->struct_size != sizeof(cattus_sp_config)) return "bad config struct";
+// struct_size versions the configuration: CATTUS_SP_CONFIG_SIZE_V1 = the fields up to progress_path (prefetch off), sizeof =
+// with prefetch and prefetch_fill.  `full` receives the caller's fields, the missing ones 0.
+const char* config_error(const cattus_sp_config* in, cattus_sp_config* full) {
+    if (!in || (in->struct_size != CATTUS_SP_CONFIG_SIZE_V1 && in->struct_size != sizeof(cattus_sp_config))) return "bad config struct";
+    memset(full, 0, sizeof *full);
+    memcpy(full, in, in->struct_size);
+    full->struct_size = sizeof *full;
+    const cattus_sp_config* c = full;
+    // speculative prefetch rests on the cache and on the sequential search: reported, not clamped
+    if (c->prefetch > 15) return "prefetch must be 0..15";
+    if (c->prefetch && c->cache_size == 0) return "prefetch needs the evaluation cache: cache_size must be > 0";
+    if (c->prefetch && c->leaves_in_flight > 1) return "prefetch is for the sequential search: leaves_in_flight must be 0 or 1";
+    if (c->prefetch && c->prefetch_fill > std::max(1u, c->batch_size)) return "prefetch_fill must not exceed batch_size";
     if (c->sim_num < 2) return "sim_num must be > 1";
     if (c->temperature_count < 1 || c->temperature_count > 8) return "temperature_count must be 1..8";
     for (uint32_t i = 0; i < c->temperature_count; i++) {
@@ -214,6 +227,7 @@ struct cattus_sp_result {
     cattus_sp_summary summary{};
     std::vector<Record> records;
     size_t record_bytes = 0;
+    uint64_t prefetch[4] = {0, 0, 0, 0};  // nominated, evaluated, hits, dropped
 };
 
 SP_API const char* cattus_sp_last_error(void) { return g_err.c_str(); }
@@ -234,10 +248,12 @@ SP_API int cattus_sp_run(int game, const cattus_sp_config* c, cattus_net_eval_fn
         g_err = "bad arguments";
         return -1;
     }
-    if (const char* why = config_error(c)) {
+    cattus_sp_config full;
+    if (const char* why = config_error(c, &full)) {
         g_err = why;
         return -1;
     }
+    c = &full;
     *out = nullptr;
     int rc = -1;
     dispatch(game, [&](auto g) -> int {
@@ -264,6 +280,8 @@ SP_API int cattus_sp_run(int game, const cattus_sp_config* c, cattus_net_eval_fn
         s.steady_seconds = r.steady_seconds, s.steady_node_evals = r.steady_node_evals;
         s.steady_plies = r.steady_plies, s.steady_batches = r.steady_batches;
         s.adjudicated = r.adjudicated;
+        res->prefetch[0] = m.prefetch_nominated, res->prefetch[1] = m.prefetch_evaluated;
+        res->prefetch[2] = m.prefetch_hits, res->prefetch[3] = m.prefetch_dropped;
         res->record_bytes = Serializer<G>::RECORD_BYTES;
         if (!keep_records) res->records.clear();
         std::sort(res->records.begin(), res->records.end(), [](const Record& a, const Record& b) {
@@ -290,6 +308,12 @@ SP_API int cattus_sp_result_records(const cattus_sp_result* r, uint8_t* bytes, u
     return (int)r->records.size();
 }
 
+SP_API int cattus_sp_result_prefetch(const cattus_sp_result* r, uint64_t out[4]) {
+    if (!r || !out) return -1;
+    std::copy(r->prefetch, r->prefetch + 4, out);
+    return 0;
+}
+
 SP_API void cattus_sp_result_free(cattus_sp_result* r) { delete r; }
 
 SP_API int cattus_sp_stub_net(void* ctx, const uint64_t* planes, uint32_t n, float* policy, float* value) {
@@ -314,10 +338,12 @@ SP_API int64_t cattus_sp_trace_game_ex(int game, const cattus_sp_config* c, catt
         g_err = "bad arguments";
         return -1;
     }
-    if (const char* why = config_error(c)) {
+    cattus_sp_config full;
+    if (const char* why = config_error(c, &full)) {
         g_err = why;
         return -1;
     }
+    c = &full;
     int64_t written = -1;
     dispatch(game, [&](auto g) -> int {
         typedef decltype(g) G;
@@ -333,6 +359,7 @@ SP_API int64_t cattus_sp_trace_game_ex(int game, const cattus_sp_config* c, catt
         uint32_t plies = 0, searched = 0;
         std::vector<float> policy(G::MOVES);
         std::vector<typename G::Move> legal;
+        std::vector<typename G::Position> noms;
         while (searched < max_plies) {
             if (gs.status().finished) break;
             typename G::Move m{};
@@ -359,6 +386,21 @@ SP_API int64_t cattus_sp_trace_game_ex(int game, const cattus_sp_config* c, catt
                             return 0;
                         }
                         vf.finish(pend, policy.data(), value, ev);
+                        // cfg.prefetch: what the driver does at this stop, one nominee at a time -- named, rolled back, evaluated
+                        // into the cache and never delivered; the visit counts below must not notice
+                        if (cfg.prefetch) {
+                            cur.nominate(cfg.prefetch, noms);
+                            for (const auto& np : noms) {
+                                PendingLeaf<G> sp;
+                                Evaluation<G> sev;
+                                if (vf.prepare(np, sp, sev, true)) continue;
+                                if (net(ctx, sp.planes, 1, policy.data(), &value) != 0) {
+                                    g_err = "network callback failed";
+                                    return 0;
+                                }
+                                vf.finish(sp, policy.data(), value, sev, true);
+                            }
+                        }
                     }
                     cur.deliver(ev);
                 }
@@ -417,6 +459,72 @@ SP_API int cattus_sp_test_temperature_choice(uint64_t seed, const float* probs, 
     std::fill(counts, counts + k, 0u);
     for (uint32_t d = 0; d < draws; d++) counts[sample_with_temperature(rng, probs, k, temperature, w)]++;
     return 0;
+}
+
+SP_API int cattus_sp_test_nominate(int game, const char* pos, uint32_t sims, uint32_t k, uint32_t out[7], char* nominee_strs,
+                                   char* lif_strs, uint32_t str_stride) {
+    if (!out || !nominee_strs || !lif_strs || k < 1 || k > 15 || str_stride < 2) return -1;
+    int rc = -1;
+    dispatch(game, [&](auto g) -> int {
+        typedef decltype(g) G;
+        typename G::Position start = G::Position::initial();
+        if (pos && !parse_pos<G>(pos, start)) return 0;
+        uint32_t info[2] = {(uint32_t)G::MOVES, (uint32_t)(G::PLANES * G::PLANE_WORDS)};
+        MctsParams mp;
+        mp.sim_num = sims + 64;  // the budget is not what ends this search
+        Metrics metrics;
+        NetValueFunction<G> vf(NetHandle{cattus_sp_stub_net, info}, 100000, &metrics);
+        const std::vector<typename G::Position> history{start};
+        if (start.status().finished) return 0;
+        MctsPlayer<G> seq(mp, 1);
+        seq.begin_search(history);
+        std::vector<float> policy(G::MOVES);
+        auto evaluate = [&](const typename G::Position& p, Evaluation<G>& ev) {
+            PendingLeaf<G> pend;
+            if (vf.prepare(p, pend, ev)) return;
+            float value = 0;
+            cattus_sp_stub_net(info, pend.planes, 1, policy.data(), &value);
+            vf.finish(pend, policy.data(), value, ev);
+        };
+        Evaluation<G> ev;
+        while (seq.sims_done() < sims) {
+            if (seq.advance(history) != MctsPlayer<G>::NEED_EVAL) return 0;
+            evaluate(seq.pending_position(), ev);
+            seq.deliver(ev);
+        }
+        MctsPlayer<G> lif = seq;  // the same tree, about to take the same step with k + 1 leaves in flight
+        lif.set_leaves_in_flight(k + 1);
+        if (seq.advance(history) != MctsPlayer<G>::NEED_EVAL || lif.advance(history) != MctsPlayer<G>::NEED_EVAL) return 0;
+        const typename G::Position pending = seq.pending_position();
+        const auto visits = seq.root_visits();
+        const uint32_t done = seq.sims_done();
+        const uint64_t rng = seq.rng_state();
+        std::vector<typename G::Position> noms;
+        seq.nominate(k, noms);
+        auto put = [&](char* dst, uint32_t i, const typename G::Position& p) {
+            const std::string s = pos_string<G>(p);
+            memset(dst + (size_t)i * str_stride, 0, str_stride);
+            memcpy(dst + (size_t)i * str_stride, s.data(), std::min<size_t>(s.size(), str_stride - 1));
+        };
+        out[0] = (uint32_t)noms.size(), out[1] = lif.pending_count(), out[2] = lif.sims_done() - done;
+        out[3] = (uint32_t)seq.vl_held(), out[4] = seq.pending_nodes();
+        out[5] = seq.sims_done() == done && seq.root_visits() == visits && seq.rng_state() == rng && seq.pending_count() == 1 &&
+                 seq.pending_position() == pending;
+        bool clean = true;
+        for (size_t i = 0; i < noms.size(); i++) {
+            clean &= !noms[i].status().finished && !(noms[i] == pending);
+            for (size_t j = 0; j < i; j++) clean &= !(noms[i] == noms[j]);
+            put(nominee_strs, (uint32_t)i, noms[i]);
+        }
+        out[6] = clean;
+        for (uint32_t i = 0; i < lif.pending_count(); i++) put(lif_strs, i, lif.pending_position(i));
+        // the pending leaf still takes its evaluation as if nothing had happened
+        evaluate(seq.pending_position(), ev);
+        if (!seq.deliver(ev) || seq.sims_done() != done + 1) return 0;
+        rc = 0;
+        return 1;
+    });
+    return rc;
 }
 
 SP_API int cattus_sp_play_moves(int game, const uint16_t* moves, uint32_t n, uint32_t* plies_played) {

@@ -202,6 +202,50 @@ class MctsPlayer {
     uint32_t pending_count() const { return inflight_n_; }
     const Position& pending_position(uint32_t i = 0) const { return nodes_[inflight_[i].leaf].pos; }
 
+    // Speculative nomination (not in the reference).  A sequential search (leaves_in_flight <= 1) that stopped at
+    // NEED_EVAL names up to k further unexpanded leaves it is likely to ask for next: the leaves that
+    // leaves_in_flight = k + 1 would have taken behind the pending one -- a virtual loss on the pending path and on
+    // every nominee's path, then select again.  The positions are copied to `out` and EVERYTHING is rolled back: every
+    // vl is 0 again and only leaf 0 is pending, exactly as before the call.  A nominee is never delivered; the caller
+    // may evaluate it into the evaluation cache, where the search finds it if it does get there.  Touches neither
+    // rng_, sims_done_ nor any n or w; it may make child nodes (see the note on lazy nodes at the top of the file).
+    //   * a selection that runs into the pending leaf or an earlier nominee ends the call (with the virtual losses
+    //     in place the next selection would end there too), as advance() does;
+    //   * a terminal node or a repetition is not nominated: advance() would back its score up, which is not ours to
+    //     do, so its path gets a virtual loss like a nominee's and the selection goes on (a bounded number of times);
+    //   * a leaf whose position equals the pending one's or an earlier nominee's (a transposition) uses up one of the k
+    //     places and is not returned.
+    uint32_t nominate(uint32_t k, std::vector<Position>& out) {
+        out.clear();
+        if (inflight_n_ != 1 || delivered_ != 0 || params_.leaves_in_flight > 1) return 0;
+        k = std::min(k, MAX_IN_FLIGHT - 1);
+        nom_edges_.clear();
+        nom_nodes_.clear();
+        auto hold = [&](const std::vector<uint32_t>& path) {
+            for (uint32_t e : path) edges_[e].vl++, nom_edges_.push_back(e);
+        };
+        hold(inflight_[0].path);
+        const uint32_t pending_leaf = inflight_[0].leaf;
+        uint32_t places = 0;
+        for (uint32_t tries = 0; places < k && tries < 2 * k + 2 && sims_done_ + 1 + places < params_.sim_num; tries++) {
+            select(nom_path_);
+            const uint32_t leaf = nom_path_.empty() ? root_ : edges_[nom_path_.back()].target;
+            if (nodes_[leaf].pending) break;
+            hold(nom_path_);
+            if (detect_repetition(nom_path_) || nodes_[leaf].status().finished) continue;
+            nodes_[leaf].pending = 1;
+            nom_nodes_.push_back(leaf);
+            places++;
+            const Position& pos = nodes_[leaf].pos;
+            bool seen = pos == nodes_[pending_leaf].pos;
+            for (size_t i = 0; i < out.size() && !seen; i++) seen = out[i] == pos;
+            if (!seen) out.push_back(pos);
+        }
+        for (uint32_t e : nom_edges_) edges_[e].vl--;
+        for (uint32_t nd : nom_nodes_) nodes_[nd].pending = 0;
+        return (uint32_t)out.size();
+    }
+
     // second half of a simulation: create_children, root noise, backpropagate (mcts/mod.rs:179-194)
     // Returns false (and changes nothing) for an index that is not waiting: out of range or delivered before.
     bool deliver(const Evaluation<G>& ev) { return deliver(0, ev); }
@@ -264,6 +308,20 @@ class MctsPlayer {
         inflight_n_ = delivered_ = 0;
     }
     size_t tree_nodes() const { return nodes_.size(); }
+    // what nominate() must leave alone (known-answer hook): virtual losses held, nodes waiting, simulations, random stream
+    uint64_t vl_held() const {
+        uint64_t s = 0;
+        for (const Edge& e : edges_) s += e.vl;
+        return s;
+    }
+    uint32_t pending_nodes() const {
+        uint32_t s = 0;
+        for (const Node& n : nodes_) s += n.pending;
+        return s;
+    }
+    uint32_t sims_done() const { return sims_done_; }
+    uint64_t rng_state() const { return rng_.s; }
+    void set_leaves_in_flight(uint32_t k) { params_.leaves_in_flight = k; }
 
    private:
     struct Node {
@@ -486,6 +544,8 @@ class MctsPlayer {
     };
     InFlight inflight_[MAX_IN_FLIGHT];
     uint32_t inflight_n_ = 0, delivered_ = 0;
+    // nominate(): the selection's path, and what to roll back (an edge once per virtual loss it got; nodes marked pending)
+    std::vector<uint32_t> nom_path_, nom_edges_, nom_nodes_;
     struct HistEntry {
         uint64_t hash;
         const Position* pos;  // into the caller's history vector, which outlives the search

@@ -53,6 +53,9 @@ struct Metrics {
     alignas(64) std::atomic<uint64_t> activation_count{0};
     std::atomic<uint64_t> node_evals{0};
     std::atomic<uint64_t> plies{0};  // moves played (a game's records are counted in `positions` only when it ends)
+    // speculative leaf prefetch (SelfPlayConfig::prefetch): positions nominated, of them evaluated in a batch's empty rows,
+    // real leaves served by such a row's cache entry, and nominees that never reached the network
+    std::atomic<uint64_t> prefetch_nominated{0}, prefetch_evaluated{0}, prefetch_hits{0}, prefetch_dropped{0};
     double run_duration_ema = 0.0, search_duration_ema = 0.0;  // RunningAverage eps 0.99 (util/metric.rs)
     std::mutex mu;
     void set_run(double s) {
@@ -76,31 +79,45 @@ template <typename G>
 class EvalCache {
    public:
     explicit EvalCache(size_t max_size) : max_size_(max_size ? max_size : 1) {}
-    bool get(const typename G::Position& pos, Evaluation<G>& out) {
+    // *from_spec: the entry was put there by a speculative row and no real leaf had asked for it yet (asked now: the mark goes)
+    bool get(const typename G::Position& pos, Evaluation<G>& out, bool* from_spec = nullptr) {
         const uint64_t h = pos.hash();
         Shard& s = shards_[h % SHARDS];
         std::lock_guard<std::mutex> lk(s.mu);
         auto range = s.map.equal_range(h);
         for (auto it = range.first; it != range.second; ++it)
-            if (it->second.first == pos) {
-                out = it->second.second;
+            if (it->second.pos == pos) {
+                out = it->second.ev;
+                if (from_spec) *from_spec = it->second.spec, it->second.spec = false;
                 return true;
             }
         return false;
     }
+    bool contains(const typename G::Position& pos) {
+        const uint64_t h = pos.hash();
+        Shard& s = shards_[h % SHARDS];
+        std::lock_guard<std::mutex> lk(s.mu);
+        auto range = s.map.equal_range(h);
+        for (auto it = range.first; it != range.second; ++it)
+            if (it->second.pos == pos) return true;
+        return false;
+    }
     // returns false if the position was already present (the reference then returns the cached value)
-    bool insert(const typename G::Position& pos, const Evaluation<G>& ev, Evaluation<G>* existing) {
+    // spec: the result of a speculative row; the entry is marked until a real leaf asks for it.  A real leaf that was
+    // evaluated all the same (it went to the network before the speculative row came back) takes the mark away.
+    bool insert(const typename G::Position& pos, const Evaluation<G>& ev, Evaluation<G>* existing, bool spec = false) {
         const uint64_t h = pos.hash();
         {
             Shard& s = shards_[h % SHARDS];
             std::lock_guard<std::mutex> lk(s.mu);
             auto range = s.map.equal_range(h);
             for (auto it = range.first; it != range.second; ++it)
-                if (it->second.first == pos) {
-                    if (existing) *existing = it->second.second;
+                if (it->second.pos == pos) {
+                    if (existing) *existing = it->second.ev;
+                    if (!spec) it->second.spec = false;
                     return false;
                 }
-            s.map.emplace(h, std::make_pair(pos, ev));
+            s.map.emplace(h, Entry{pos, ev, spec});
         }
         // "remove the oldest while len >= max_size, then insert" (cache.rs:62-70): after either order of the two
         // steps the cache holds the newest max_size positions
@@ -121,7 +138,7 @@ class EvalCache {
             std::lock_guard<std::mutex> lk(os.mu);
             auto r = os.map.equal_range(oh);
             for (auto it = r.first; it != r.second; ++it)
-                if (it->second.first == victim) {
+                if (it->second.pos == victim) {
                     os.map.erase(it);
                     break;
                 }
@@ -154,9 +171,14 @@ class EvalCache {
         ~SpinGuard() { f.clear(std::memory_order_release); }
     };
     static constexpr size_t SHARDS = 64;
+    struct Entry {
+        typename G::Position pos;
+        Evaluation<G> ev;
+        bool spec;  // from a speculative row, not yet asked for by a search
+    };
     struct alignas(64) Shard {
         std::mutex mu;
-        std::unordered_multimap<uint64_t, std::pair<typename G::Position, Evaluation<G>>> map;
+        std::unordered_multimap<uint64_t, Entry> map;
     };
     Shard shards_[SHARDS];
     alignas(64) std::atomic_flag fifo_lock_ = ATOMIC_FLAG_INIT;
@@ -183,13 +205,20 @@ class NetValueFunction {
     NetHandle net() const { return net_; }
 
     // flip_pos_if_needed + cache probe + to_planes (net/mod.rs:79-94). true = served from the cache.
-    bool prepare(const typename G::Position& position, PendingLeaf<G>& pend, Evaluation<G>& out) {
+    // speculative: a nominee, not a leaf of a search -- it counts in no cache metric and `out` is left alone
+    bool prepare(const typename G::Position& position, PendingLeaf<G>& pend, Evaluation<G>& out, bool speculative = false) {
         pend.flipped = position.turn() != PLAYER1;
         pend.pos = pend.flipped ? position.flipped() : position;
-        if (cache_.get(pend.pos, out)) {
-            metrics_->cache_hits++;
-            unflip(out, pend.flipped);
-            return true;
+        if (speculative) {
+            if (cache_.contains(pend.pos)) return true;
+        } else {
+            bool from_spec = false;
+            if (cache_.get(pend.pos, out, &from_spec)) {
+                metrics_->cache_hits++;
+                if (from_spec) metrics_->prefetch_hits++;
+                unflip(out, pend.flipped);
+                return true;
+            }
         }
         pend.pos.planes(pend.planes);
         if (net_.legal_fn) {
@@ -201,20 +230,30 @@ class NetValueFunction {
         return false;
     }
     // the same tail as finish() for a network that returned the legal-move probabilities itself
-    void finish_legal(const PendingLeaf<G>& pend, const float* probs, float value, Evaluation<G>& out) {
+    // speculative (here and in finish()): the row of a nominee -- its result goes into the cache, marked, and nowhere else
+    void finish_legal(const PendingLeaf<G>& pend, const float* probs, float value, Evaluation<G>& out, bool speculative = false) {
         out.probs.clear();
         for (size_t i = 0; i < pend.moves.size(); i++) out.probs.emplace_back(pend.moves[i], probs[i]);
         out.value = value;
+        if (speculative) {
+            cache_.insert(pend.pos, out, nullptr, true);
+            return;
+        }
         if (cache_.insert(pend.pos, out, &out)) metrics_->cache_misses++;
         else metrics_->cache_hits++;
         unflip(out, pend.flipped);
     }
+    bool cached(const typename G::Position& flipped_pos) { return cache_.contains(flipped_pos); }
     // calc_moves_probs + cache insert + flip_score_if_needed (net/mod.rs:100-119, cache.rs:49-74, net/mod.rs:166-182)
-    void finish(const PendingLeaf<G>& pend, const float* logits, float value, Evaluation<G>& out) {
+    void finish(const PendingLeaf<G>& pend, const float* logits, float value, Evaluation<G>& out, bool speculative = false) {
         static thread_local std::vector<typename G::Move> moves;
         pend.pos.legal_moves(moves);
         softmax_legal(moves, logits, out.probs);
         out.value = value;
+        if (speculative) {
+            cache_.insert(pend.pos, out, nullptr, true);
+            return;
+        }
         if (cache_.insert(pend.pos, out, &out)) metrics_->cache_misses++;
         else metrics_->cache_hits++;  // someone else inserted it meanwhile: `out` now holds the cached value
         unflip(out, pend.flipped);
@@ -333,6 +372,13 @@ struct SelfPlayConfig {
     // this process plays global game indices first_game + k*game_stride, k = 0..games_num-1
     uint32_t first_game = 0, game_stride = 1;
     uint32_t max_game_plies = 0;  // > 0 (not in the reference): adjudicate a draw after this many plies
+    // Speculative leaf prefetch (not in the reference; off by default).  prefetch = k > 0: a sequential search that stops
+    // for the network also nominates up to k leaves it is likely to ask for next (MctsPlayer::nominate); batches with
+    // fewer than prefetch_fill real leaves (0 = batch_size) carry nominees in their empty rows, and those results go into
+    // the evaluation cache only.  The search itself is untouched -- it finds its next leaf in the cache or it does not --
+    // so visit counts and records are those of prefetch = 0; what changes is how many network round trips a game takes.
+    // Needs cache_size > 0 and leaves_in_flight <= 1.
+    uint32_t prefetch = 0, prefetch_fill = 0;
     // failure containment (include/cattus_selfplay.h): explicit game indices of a re-queue; a progress file that gets one
     // line per finished game
     std::vector<uint32_t> game_list;
@@ -414,6 +460,17 @@ class SelfPlayRunner {
         std::condition_variable cv_work, cv_eval;
         std::deque<uint32_t> ready;
         std::vector<uint32_t> pending[2];
+        // Speculative prefetch (cfg_.prefetch > 0): `spec[net]` holds nominees (MctsPlayer::nominate) that are worth a row.
+        // An evaluation thread composes its batch from pending[net] as ever and then tops it up from spec[net], newest
+        // first, while the batch has fewer than `fill` leaves; a full batch of real leaves carries none.  The queue is
+        // bounded and its oldest entries drop out: a nominee that has waited long names a leaf its search has passed by.
+        std::deque<PendingLeaf<G>> spec[2];
+        const uint32_t fill = cfg_.prefetch ? std::min(cfg_.prefetch_fill ? cfg_.prefetch_fill : cfg_.batch_size, cfg_.batch_size) : 0;
+        const size_t spec_cap = std::max<size_t>(64, 2 * (size_t)cfg_.batch_size);
+        // Naming leaves costs the search threads k selections a stop, so they name only as many as the batches have had rows
+        // for: a batch credits the rows it had free below `fill`, a stop that queues nominees spends them, and at no credit a
+        // stop names nothing (batches that run full: the searches pay one load).  A queue's worth to start with.
+        spec_room_[0] = spec_room_[1] = (int64_t)spec_cap;
         uint32_t busy = 0, done = 0;
         bool finished = false;
         int rc = 0;
@@ -513,6 +570,14 @@ class SelfPlayRunner {
                     if (sl.state == Slot::WAIT_EVAL) {
                         for (uint32_t q = 0; q < sl.npend; q++)
                             if (!sl.leaf[q].cached) pending[sl.netid].push_back(mine[i] * MctsPlayer<G>::MAX_IN_FLIGHT + q);
+                        if (!sl.spec_out.empty()) {
+                            auto& sq = spec[sl.netid];
+                            for (auto& pl : sl.spec_out) sq.push_back(std::move(pl));
+                            sl.spec_out.clear();
+                            uint32_t over = 0;
+                            for (; sq.size() > spec_cap; over++) sq.pop_front();
+                            if (over) metrics_.prefetch_dropped += over;
+                        }
                     } else {
                         done++, wake = true;
                     }
@@ -537,6 +602,8 @@ class SelfPlayRunner {
         uint32_t inflight = 0;
         auto evaluator = [&]() {
             std::vector<uint32_t> who;
+            std::vector<PendingLeaf<G>> specs;  // speculative rows of the batch
+            std::vector<uint64_t> hashes;       // position hashes of the batch's rows, while it has speculative ones
             std::unique_lock<std::mutex> lk(mu);
             for (;;) {
                 if (done == nslots || rc != 0 || finished) break;
@@ -556,27 +623,56 @@ class SelfPlayRunner {
                 pending[netid].erase(pending[netid].begin(), pending[netid].begin() + n);
                 bb.refs = (uint32_t)n;
                 inflight++;
+                if (n < fill && spec_room_[netid].load(std::memory_order_relaxed) < (int64_t)spec_cap) spec_room_[netid] += (int64_t)(fill - n);
+                specs.clear();  // the top-up: the newest nominees, as many as rows are free below `fill`
+                for (auto& sq = spec[netid]; n + specs.size() < fill && !sq.empty(); sq.pop_back()) specs.push_back(std::move(sq.back()));
                 lk.unlock();
                 int erc = 0;
-                for (size_t k = 0; k < n; k++) {
-                    constexpr uint32_t MIF = MctsPlayer<G>::MAX_IN_FLIGHT;
-                    const PendingLeaf<G>& pl = slots[who[k] / MIF].pend[who[k] % MIF];
+                auto put_row = [&](size_t k, const PendingLeaf<G>& pl) {
                     memcpy(bb.planes + k * words, pl.planes, words * 8);
                     if (legal) {
-                        if (pl.legal_count > LEGAL_STRIDE) erc = -5;
                         bb.legal_cnt[k] = (uint16_t)std::min<uint32_t>(pl.legal_count, LEGAL_STRIDE);
                         memcpy(bb.legal_idx + k * LEGAL_STRIDE, pl.legal_idx, (size_t)bb.legal_cnt[k] * 2);
                     }
+                };
+                for (size_t k = 0; k < n; k++) {
+                    constexpr uint32_t MIF = MctsPlayer<G>::MAX_IN_FLIGHT;
+                    const PendingLeaf<G>& pl = slots[who[k] / MIF].pend[who[k] % MIF];
+                    if (legal && pl.legal_count > LEGAL_STRIDE) erc = -5;
+                    put_row(k, pl);
                 }
-                NetHandle net = netid == 0 ? vf1_.net() : vf2_.net();
+                auto& vf = netid == 0 ? vf1_ : vf2_;
+                // Speculative rows n .. n + m: a nominee goes along unless its position has reached the cache since it was named,
+                // or sits in this batch already (several games, or one search at two stops, name the same leaf).
+                size_t m = 0;
+                if (!specs.empty()) {
+                    hashes.clear();
+                    for (size_t k = 0; k < n; k++) hashes.push_back(slots[who[k] / MctsPlayer<G>::MAX_IN_FLIGHT].pend[who[k] % MctsPlayer<G>::MAX_IN_FLIGHT].pos.hash());
+                    for (size_t j = 0; j < specs.size(); j++) {
+                        const uint64_t h = specs[j].pos.hash();
+                        bool drop = (legal && specs[j].legal_count > LEGAL_STRIDE) || vf.cached(specs[j].pos);
+                        for (size_t k = 0; k < n + m && !drop; k++) {
+                            if (hashes[k] != h) continue;
+                            constexpr uint32_t MIF = MctsPlayer<G>::MAX_IN_FLIGHT;
+                            drop = specs[j].pos == (k < n ? slots[who[k] / MIF].pend[who[k] % MIF].pos : specs[k - n].pos);
+                        }
+                        if (drop) continue;
+                        if (j != m) specs[m] = std::move(specs[j]);
+                        hashes.push_back(h);
+                        put_row(n + m, specs[m]);
+                        m++;
+                    }
+                    if (specs.size() > m) metrics_.prefetch_dropped += specs.size() - m;
+                }
+                NetHandle net = vf.net();
                 const auto r0 = std::chrono::steady_clock::now();
                 if (erc == 0)
-                    erc = legal ? net.legal_fn(net.ctx, bb.planes, (uint32_t)n, bb.legal_idx, bb.legal_cnt, LEGAL_STRIDE, bb.policy, bb.value)
-                                : net.fn(net.ctx, bb.planes, (uint32_t)n, bb.policy, bb.value);
+                    erc = legal ? net.legal_fn(net.ctx, bb.planes, (uint32_t)(n + m), bb.legal_idx, bb.legal_cnt, LEGAL_STRIDE, bb.policy, bb.value)
+                                : net.fn(net.ctx, bb.planes, (uint32_t)(n + m), bb.policy, bb.value);
                 if (erc == 0) {
                     metrics_.set_run(std::chrono::duration<double>(std::chrono::steady_clock::now() - r0).count());
                     metrics_.activation_count++;  // counts batches, as the reference does (net/mod.rs:68)
-                    metrics_.node_evals += n;
+                    metrics_.node_evals += n;     // real leaves only: a speculative row is nobody's simulation
                     for (size_t k = 0; k < n; k++) {
                         constexpr uint32_t MIF = MctsPlayer<G>::MAX_IN_FLIGHT;
                         auto& lf = slots[who[k] / MIF].leaf[who[k] % MIF];
@@ -584,6 +680,13 @@ class SelfPlayRunner {
                         lf.value = bb.value[k];
                         lf.batch = bi;
                     }
+                    // the speculative rows end here: into the cache, before any slot of this batch searches on
+                    Evaluation<G> ev;
+                    for (size_t j = 0; j < m; j++) {
+                        if (legal) vf.finish_legal(specs[j], bb.policy + (n + j) * row, bb.value[n + j], ev, true);
+                        else vf.finish(specs[j], bb.policy + (n + j) * row, bb.value[n + j], ev, true);
+                    }
+                    if (m) metrics_.prefetch_evaluated += m;
                 }
                 lk.lock();
                 inflight--;
@@ -612,6 +715,7 @@ class SelfPlayRunner {
             for (auto& t : evals) t.join();
         }
         for (auto& t : workers) t.join();
+        metrics_.prefetch_dropped += spec[0].size() + spec[1].size();  // named, and the run ended before a row was free
 #ifdef CATTUS_SCHED_STATS
         fprintf(stderr, "sched: workers %u  idle %.2fs  lock %.2fs  advance %.2fs  iterations %llu\n", cfg_.threads, st_wait * 1e-9,
                 st_lock * 1e-9, st_adv * 1e-9, (unsigned long long)st_iters.load());
@@ -653,6 +757,12 @@ class SelfPlayRunner {
         } leaf[MctsPlayer<G>::MAX_IN_FLIGHT];
         uint32_t npend = 0;     // leaves of the current group
         uint32_t awaiting = 0;  // of them, still at the network (guarded by the scheduler mutex)
+        // speculative prefetch: the nominees of the last stop, those of them bound for spec[netid], hashes named lately
+        static constexpr uint32_t RECENT = 32;
+        std::vector<Position> noms;
+        std::vector<PendingLeaf<G>> spec_out;
+        uint64_t recent[RECENT] = {};
+        uint32_t recent_at = 0;
         std::chrono::steady_clock::time_point search_t0;
         std::string error;
         Slot(const MctsParams& p, uint64_t seed) : p1(p, seed * 2 + 1), p2(p, seed * 2 + 2) {}
@@ -735,6 +845,7 @@ class SelfPlayRunner {
                         } else {
                             s.awaiting = to_net;
                             s.state = Slot::WAIT_EVAL;
+                            if (cfg_.prefetch) nominate(s, vf);
                             return;
                         }
                     } else {
@@ -755,6 +866,35 @@ class SelfPlayRunner {
                 }
             }
         }
+    }
+
+    // Speculative prefetch, the search's side: the slot's search has just stopped for the network; name the leaves it is
+    // likely to ask for next and leave those that are worth a row in s.spec_out (the worker hands them to spec[net] under
+    // the scheduler's lock).  A search names much the same leaves at one stop after another, so a slot remembers the
+    // hashes of what it named last and lets those go before anything is computed for them.
+    void nominate(Slot& s, NetValueFunction<G>& vf) {
+        if (spec_room_[s.netid].load(std::memory_order_relaxed) <= 0) return;  // the batches have no rows to spare
+        s.cur->nominate(cfg_.prefetch, s.noms);
+        metrics_.prefetch_nominated += s.noms.size();
+        uint32_t dropped = 0;
+        for (const Position& pos : s.noms) {
+            const uint64_t h = pos.hash();
+            bool recent = false;
+            for (uint64_t r : s.recent) recent |= r == h;
+            if (recent) {
+                dropped++;
+                continue;
+            }
+            s.recent[s.recent_at++ % Slot::RECENT] = h;
+            s.spec_out.emplace_back();
+            Evaluation<G> unused;
+            if (vf.prepare(pos, s.spec_out.back(), unused, true)) {  // in the cache already
+                s.spec_out.pop_back();
+                dropped++;
+            }
+        }
+        if (dropped) metrics_.prefetch_dropped += dropped;
+        if (!s.spec_out.empty()) spec_room_[s.netid] -= (int64_t)s.spec_out.size();
     }
 
     // write_data_entry for every stored position + win counters (self_play.rs:219-241,248-275)
@@ -820,6 +960,7 @@ class SelfPlayRunner {
     bool same_model_;
     std::string error_;
     FILE* progress_ = nullptr;  // guarded by generate_data's out_mu
+    std::atomic<int64_t> spec_room_[2];  // speculative prefetch: rows the batches of each network can still take (see generate_data)
 };
 
 }  // namespace cattus

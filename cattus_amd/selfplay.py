@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "cattus_sp_run",
     "cattus_sp_result_summary",
     "cattus_sp_result_records",
+    "cattus_sp_result_prefetch",
     "cattus_sp_result_free",
     "cattus_sp_last_error",
     "cattus_sp_stub_net",
@@ -44,6 +45,7 @@ ABI_SYMBOLS = [
     "cattus_sp_play_moves",
     "cattus_sp_test_dirichlet",
     "cattus_sp_test_temperature_choice",
+    "cattus_sp_test_nominate",
     "cattus_sp_pos_new",
     "cattus_sp_pos_free",
     "cattus_sp_pos_status",
@@ -87,7 +89,13 @@ class SpConfig(C.Structure):
         ("max_game_plies", C.c_uint32),
         ("game_list", C.POINTER(C.c_uint32)),
         ("progress_path", C.c_char_p),
+        ("prefetch", C.c_uint32),
+        ("prefetch_fill", C.c_uint32),
     ]
+
+
+# sizeof(cattus_sp_config) before prefetch / prefetch_fill were appended (CATTUS_SP_CONFIG_SIZE_V1): still accepted, both 0
+SP_CONFIG_SIZE_V1 = SpConfig.prefetch.offset
 
 
 class SpSummary(C.Structure):
@@ -143,6 +151,7 @@ def load_library():
     L.cattus_sp_run.argtypes = [C.c_int, C.POINTER(SpConfig), vp, vp, vp, vp, C.c_uint32, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(vp)]
     L.cattus_sp_result_summary.argtypes = [vp, C.POINTER(SpSummary)]
     L.cattus_sp_result_records.argtypes = [vp, vp, vp]
+    L.cattus_sp_result_prefetch.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.cattus_sp_result_free.argtypes = [vp]
     L.cattus_sp_result_free.restype = None
     L.cattus_sp_last_error.restype = C.c_char_p
@@ -153,6 +162,7 @@ def load_library():
     L.cattus_sp_play_moves.argtypes = [C.c_int, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     L.cattus_sp_test_dirichlet.argtypes = [C.c_uint64, C.c_float, C.c_uint32, C.c_uint32, vp]
     L.cattus_sp_test_temperature_choice.argtypes = [C.c_uint64, vp, C.c_uint32, C.c_float, C.c_uint32, vp]
+    L.cattus_sp_test_nominate.argtypes = [C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_char_p, C.c_char_p, C.c_uint32]
     L.cattus_sp_pos_new.argtypes = [C.c_int, C.c_char_p]
     L.cattus_sp_pos_new.restype = vp
     L.cattus_sp_pos_free.argtypes = [vp]
@@ -201,6 +211,8 @@ def make_config(
     max_game_plies: int = 0,
     game_list=None,
     progress_path=None,
+    prefetch: int = 0,
+    prefetch_fill: int = 0,
 ) -> SpConfig:
     c = SpConfig()
     c.struct_size = C.sizeof(SpConfig)
@@ -216,6 +228,9 @@ def make_config(
     c.eval_threads = eval_threads  # 0 = the driver's default (2 batches in flight)
     c.max_game_plies = max_game_plies  # > 0: adjudicate a draw after that many plies (bounded samples; not in the reference)
     c.leaves_in_flight = leaves_in_flight  # > 1: several leaves per tree at the network (virtual loss), not in the reference
+    # speculative leaf prefetch (include/cattus_selfplay.h; not in the reference): up to `prefetch` nominees per blocked search ride in
+    # the free rows of batches with fewer than prefetch_fill leaves (0 = batch_size); same records, fewer round trips.  0 = off
+    c.prefetch, c.prefetch_fill = prefetch, prefetch_fill
     # failure containment (include/cattus_selfplay.h): explicit global game indices (a re-queue) and the progress file
     if game_list is not None:
         c._game_list = np.ascontiguousarray(list(game_list), dtype=np.uint32)  # kept alive by the struct object
@@ -238,6 +253,9 @@ def config_from_engine_json(cfg: dict, **overrides) -> SpConfig:
         batch_size=cfg["model"]["batch_size"],
         threads=cfg["threads"],
         leaves_in_flight=m.get("leaves_in_flight", 1),  # extension: not a key of the reference's JSON
+        # extensions, top level next to concurrent_games: speculative leaf prefetch (off unless asked for)
+        prefetch=cfg.get("prefetch", 0),
+        prefetch_fill=cfg.get("prefetch_fill", 0),
     )
     kw.update(overrides)
     return make_config(**kw)
@@ -386,6 +404,10 @@ def run_self_play(game: str, cfg: SpConfig, net1: Net, net2: Net | None, games_n
         if n:
             L.cattus_sp_result_records(res, rec.ctypes.data, meta.ctypes.data)
         out["record_bytes"], out["record_meta"] = rec, meta
+        pf = (C.c_uint64 * 4)()
+        L.cattus_sp_result_prefetch(res, pf)
+        out["prefetch"] = int(cfg.prefetch)  # the setting; the counters below are all 0 without it
+        out["prefetch_nominated"], out["prefetch_evaluated"], out["prefetch_hits"], out["prefetch_dropped"] = (int(x) for x in pf)
         return out
     finally:
         L.cattus_sp_result_free(res)
@@ -413,6 +435,23 @@ def trace_game(game: str, cfg: SpConfig, net: Net, max_plies: int = 512, forced=
         out.append((chosen, pairs))
         w += 2 + 2 * k
     return out
+
+
+def nominate_kat(game: str, pos: str | None, sims: int, k: int) -> dict:
+    """Known-answer hook of the speculative nomination (cattus_sp_test_nominate): after `sims` simulations of a sequential search
+    from `pos`, the nominees of its next stop, the leaves a copy of the tree takes there with leaves_in_flight = k + 1, and what the
+    nomination left behind."""
+    out = (C.c_uint32 * 7)()
+    stride = 128
+    a, b = C.create_string_buffer(16 * stride), C.create_string_buffer(16 * stride)
+    if load_library().cattus_sp_test_nominate(GAMES[game], pos.encode() if pos is not None else None, sims, k, out, a, b, stride) != 0:
+        raise ValueError("no stop for the network after that many simulations, or bad arguments")
+
+    def strs(buf, n):
+        return [buf.raw[stride * i : stride * (i + 1)].split(b"\0")[0].decode() for i in range(n)]
+
+    return dict(nominees=strs(a, out[0]), lif_leaves=strs(b, out[1]), lif_finished=int(out[2]), vl_held=int(out[3]), pending_nodes=int(out[4]),
+                state_unchanged=bool(out[5]), nominees_clean=bool(out[6]))
 
 
 def play_moves(game: str, moves) -> tuple:
@@ -542,6 +581,11 @@ def write_summary(path, summary: dict):
             "model.saturated": summary.get("saturated", 0),
         },
     }
+    # speculative leaf prefetch (engine JSON "prefetch" > 0): rows evaluated for nominees (they are not in node_evals), and real
+    # leaves that found such a row's result in the cache
+    if summary.get("prefetch", 0):
+        out["metrics"]["mcts.prefetch_evaluated"] = summary["prefetch_evaluated"]
+        out["metrics"]["mcts.prefetch_hits"] = summary["prefetch_hits"]
     # model.inference.verify_every: what the shadow f32 tower found (HipEvaluator.verify_stats), summed over the models that played
     # with model.inference.device_softmax too: the priors and values a search received against the exact network's
     # (HipEvaluator.verify_prior_stats)

@@ -81,7 +81,22 @@ typedef struct cattus_sp_config {
      *   went to) is appended to this file and flushed: what survives of a process that dies later. */
     const uint32_t* game_list;
     const char* progress_path;
+    /* Speculative leaf prefetch (not in the reference).  struct_size versions the configuration: CATTUS_SP_CONFIG_SIZE_V1
+     * (the fields up to progress_path) is accepted too and means both are 0.
+     * prefetch: 0 = off (the default).  k in 1..15: a sequential search that stops for the network also nominates up to k
+     *   leaves it is likely to ask for next -- those leaves_in_flight = k + 1 would have taken, found with virtual losses
+     *   that are all rolled back.  Nominees ride in the rows a batch has free and their results go into the evaluation
+     *   cache only; the search then finds its next leaf there and goes on without a round trip.  Unlike leaves_in_flight
+     *   this does not change the search: visit counts and records are exactly those of prefetch = 0.
+     *   Needs cache_size > 0 and leaves_in_flight <= 1; anything else is reported as an error, not clamped.
+     * prefetch_fill: batches are topped up to at most this many leaves; 0 = batch_size (larger values are an error).  A
+     *   batch that has this many real leaves carries no nominee. */
+    uint32_t prefetch;
+    uint32_t prefetch_fill;
 } cattus_sp_config;
+
+/* sizeof(cattus_sp_config) before prefetch / prefetch_fill were appended */
+#define CATTUS_SP_CONFIG_SIZE_V1 offsetof(cattus_sp_config, prefetch)
 
 typedef struct cattus_sp_summary {
     uint32_t player1_wins, player2_wins, draws;
@@ -114,6 +129,13 @@ int cattus_sp_run(int game, const cattus_sp_config* cfg, cattus_net_eval_fn net1
 int cattus_sp_result_summary(const cattus_sp_result* r, cattus_sp_summary* out);
 /* bytes: [records][record_bytes]; meta: [records][3] = game_idx, pos_idx, dir(0/1) */
 int cattus_sp_result_records(const cattus_sp_result* r, uint8_t* bytes, uint32_t* meta);
+/* Speculative prefetch counters of the run (all 0 with prefetch off): out = {nominated, evaluated, hits, dropped}.
+ * nominated: positions the searches named; evaluated: of them, evaluated in a batch's free rows (they count in no
+ * node_evals; their batches count in activation_count as any batch does); hits: real leaves found in the cache whose entry
+ * such a row had put there -- each a round trip the search did not make; dropped: nominees that never reached the network
+ * (named a moment ago already, in the cache by then, in the batch twice, pushed out of the bounded queue, or left over at
+ * the end).  nominated == evaluated + dropped. */
+int cattus_sp_result_prefetch(const cattus_sp_result* r, uint64_t out[4]);
 void cattus_sp_result_free(cattus_sp_result* r);
 const char* cattus_sp_last_error(void);
 
@@ -147,6 +169,19 @@ int cattus_sp_play_moves(int game, const uint16_t* moves, uint32_t n, uint32_t* 
 int cattus_sp_test_dirichlet(uint64_t seed, float alpha, uint32_t k, uint32_t draws, double* out);
 int cattus_sp_test_temperature_choice(uint64_t seed, const float* probs, uint32_t k, float temperature, uint32_t draws,
                                       uint32_t* counts);
+
+/* Known-answer hook for speculative nomination (MctsPlayer::nominate, what cfg.prefetch runs).  From position `pos` (as for
+ * cattus_sp_pos_new) a sequential search with the stand-in network runs `sims` simulations; at its next stop for the network
+ * it nominates up to k leaves.  A copy of the same tree taken just before that stop runs the same step with
+ * leaves_in_flight = k + 1.
+ * out[0] nominees, out[1] leaves the copy took (the first is the pending leaf), out[2] simulations the copy finished on the
+ * way (terminal nodes and repetitions: it backs them up, a nomination must not), and after the nomination: out[3] sum of all
+ * virtual losses, out[4] nodes pending, out[5] 1 if simulation count, root visit counts, random stream and the pending
+ * position are what they were before it, out[6] 1 if no nominee is a finished position, the pending one, or there twice.
+ * nominee_strs / lif_strs: [16][str_stride] position strings (cattus_sp_pos_str).  Returns 0, or -1 (no stop for the network
+ * after `sims` simulations, or bad arguments). */
+int cattus_sp_test_nominate(int game, const char* pos, uint32_t sims, uint32_t k, uint32_t out[7], char* nominee_strs,
+                            char* lif_strs, uint32_t str_stride);
 
 /* ---- position handles (rule tests) ---------------------------------------------------------- */
 typedef struct cattus_pos cattus_pos;
