@@ -330,6 +330,9 @@ enum class TowerKind {
     // 0.93 at 160, 1.53 | 1.01 at 192, 1.77 | 1.25 at 256, scripts/by_batch_forms.py); cattus_eval_config.tower_form forbids / forces it.
     Wino16,  // the 16-frequencies kernel (kernels_wino.hip)
     Wino4,   // the 4-frequencies x 2x2-blocks kernel (kernels_wino4.hip) wherever it covers the shape; same bits (CATTUS_WINO_KERNEL=k16|k4)
+    // the same tower with every layer behind the stem in Winograd F(4x4, 3x3) form (kernels_winof4.hip): only for tower_form WINOGRAD_F4,
+    // never by AUTO; other bits than the F(2x2) kinds, activations capped at WINOF4_ACT_MAX, always one launch per layer
+    WinoF4,
 };
 struct TowerPlan {
     TowerKind kind = TowerKind::Generic;
@@ -339,7 +342,7 @@ struct TowerPlan {
     // a layer has more tiles than the device has CUs (CATTUS_WINO_PERSIST=0: per-layer launches) -- for the batches one_launch_now() admits
     bool one_launch = false;
     bool tuned() const { return kind != TowerKind::Simple && kind != TowerKind::Generic; }  // the MFMA NHWC towers
-    bool wino() const { return kind == TowerKind::Wino16 || kind == TowerKind::Wino4; }
+    bool wino() const { return kind == TowerKind::Wino16 || kind == TowerKind::Wino4 || kind == TowerKind::WinoF4; }  // f32 rows between the layers
 };
 
 }  // namespace
@@ -494,6 +497,12 @@ int upload_conv(cattus_eval* e, ConvLayer& L, const Folded& f, uint32_t cout, ui
     int rc;
     if (!e->plan.tuned()) return (rc = up(L.b, f.b)) ? rc : up(L.w, f.w);
     const ConvShape s{cout, cin, e->fpad, stem ? e->cpad0 : e->fpad};
+    if (e->plan.kind == TowerKind::WinoF4 && !stem) {
+        std::vector<int> sh;
+        const std::vector<double> U = winof4_transform(f, s, &sh);
+        if ((rc = up(L.b, bias_and_scales(f, s, &sh)))) return rc;
+        return up(L.w, winof4_u(U, s, sh), &e->arena);
+    }
     if (e->plan.wino() && !stem) {
         std::vector<int> sh;
         const std::vector<double> U = wino_transform(f, s, &sh);
@@ -553,7 +562,9 @@ int build(cattus_eval* e, const float* p, const Calibration* cal) {
     int rc;
     e->stream_shifts.assign(F, 0);
     if (act_f16_family(e->act) && e->stream_shift_on) {
-        if (cal) e->stream_shifts = calibrated_stream_shifts(cal->s2, cal->abs_max), e->stream_shift = stream_shift_global(cal->s2);
+        // (the F(4x4) form's cap is 25x tighter: its headroom is a quarter of that cap, as the default is of the F(2x2) form's)
+        const double headroom = plan.kind == TowerKind::WinoF4 ? WINOF4_CAL_HEADROOM : STREAM_CAL_HEADROOM;
+        if (cal) e->stream_shifts = calibrated_stream_shifts(cal->s2, cal->abs_max, headroom), e->stream_shift = stream_shift_global(cal->s2);
         else e->stream_shifts = choose_stream_shift(d, p, &e->stream_shift);
     }
     const std::vector<int>& tk = e->stream_shifts;
@@ -848,9 +859,10 @@ struct Forward {
         return a;
     }
 
-    // Wino16 / Wino4: the stem on the direct kernel, every layer behind it in Winograd form, f32 rows between the layers
+    // Wino16 / Wino4 / WinoF4: the stem on the direct kernel, every layer behind it in Winograd form, f32 rows between the layers
     int wino() {
-        conv_mfma(e->stem, L.x0.p, nullptr, a, CONV_OUT_F32 | CONV_WINO_IN, true);
+        const bool f4 = e->plan.kind == TowerKind::WinoF4;
+        conv_mfma(e->stem, L.x0.p, nullptr, a, CONV_OUT_F32 | (f4 ? CONV_WINOF4_IN : CONV_WINO_IN), true);
         seen(0, a, tower_source(0));
         if (!obs && one_launch_now(e, nb)) {
             // every layer behind the stem in ONE launch: counters and error word zeroed ahead of it on the same stream, the error word
@@ -866,7 +878,7 @@ struct Forward {
             HIP_TRY(hipMemcpyAsync(L.h_tower_err.p, tower_err, 4, hipMemcpyDeviceToHost, st));
             return CATTUS_OK;
         }
-        const auto launch = e->plan.kind == TowerKind::Wino4 ? launch_conv3x3_wino4 : launch_conv3x3_wino;
+        const auto launch = f4 ? launch_conv3x3_winof4 : e->plan.kind == TowerKind::Wino4 ? launch_conv3x3_wino4 : launch_conv3x3_wino;
         auto conv = [&](const ConvLayer& c, const float* in, const float* res, float* out) {
             hipEvent_t s0 = ev(), s1 = ev();
             launch(in, c.w.p, c.b.as<float>(), res, out, nb, FP, FP, st, s0, s1, e->conv_opts.saturated);
@@ -925,6 +937,7 @@ int enqueue_forward(cattus_eval* e, Lane& L, const uint64_t* d_planes, uint32_t 
         case TowerKind::Resident64Split: f.heads_mfma(f.resident64_split()); break;
         case TowerKind::Wino16:
         case TowerKind::Wino4:
+        case TowerKind::WinoF4:
             if (int rc = f.wino()) return rc;
             f.heads_mfma(f.a);
             break;
@@ -1242,6 +1255,7 @@ CATTUS_API const char* cattus_hip_tower_kernel(const cattus_eval* e) {
         case TowerKind::Resident64Split: return "tower64_split_kernel";
         case TowerKind::Wino16: return "conv3x3_wino_kernel";
         case TowerKind::Wino4: return one_launch_now(e, e->bpad) ? "tower_wino4_kernel" : "conv3x3_wino4_kernel";
+        case TowerKind::WinoF4: return "conv3x3_winof4_kernel";
         case TowerKind::PerLayer: break;
     }
     return e->act != Act::F16S ? "conv3x3_mfma_v2_kernel" : e->plan.w_frag ? "conv3x3_splitw_kernel" : "conv3x3_split_kernel";
@@ -1320,11 +1334,18 @@ int resolve_plan(const cattus_net_desc& d, const cattus_eval_config& cfg, const 
     const bool wino_covers = tuned && act == Act::F16S && d.blocks > 0 && (k4 ? wino4_supported : wino_supported)(bpad, fpad, fpad, d.board);
     if (cfg.tower_form == CATTUS_TOWER_WINOGRAD && !wino_covers)
         return fail(CATTUS_E_UNSUPPORTED, "tower_form WINOGRAD needs dtype f16x2, an 8x8 board, at least one residual block and a multiple of 64 filters");
+    // WINOGRAD_F4: the F(4x4, 3x3) form, only when asked for; the coverage of WINOGRAD
+    const bool winof4_covers = tuned && act == Act::F16S && d.blocks > 0 && winof4_supported(bpad, fpad, fpad, d.board);
+    if (cfg.tower_form == CATTUS_TOWER_WINOGRAD_F4 && !winof4_covers)
+        return fail(CATTUS_E_UNSUPPORTED, "tower_form WINOGRAD_F4 needs dtype f16x2, an 8x8 board, at least one residual block and a multiple of 64 filters (at least 128)");
     TowerPlan& p = *plan = TowerPlan();
     p.w_frag = tuned && act == Act::F16S && !sw.starts("CATTUS_SPLIT_W", '0');
     const bool resident = tuned && fpad == 64 && !sw.starts("CATTUS_TOWER64", '0');
     if (!tuned) p.kind = simple ? TowerKind::Simple : TowerKind::Generic;
-    else if (wino_covers && (cfg.tower_form == CATTUS_TOWER_WINOGRAD || (cfg.tower_form == CATTUS_TOWER_AUTO && cfg.max_batch > 128))) {
+    else if (cfg.tower_form == CATTUS_TOWER_WINOGRAD_F4) {
+        p.kind = TowerKind::WinoF4;
+        p.inplace = !sw.starts("CATTUS_WINO_INPLACE", '0');  // never one launch for the tower
+    } else if (wino_covers && (cfg.tower_form == CATTUS_TOWER_WINOGRAD || (cfg.tower_form == CATTUS_TOWER_AUTO && cfg.max_batch > 128))) {
         p.kind = k4 ? TowerKind::Wino4 : TowerKind::Wino16;
         p.inplace = !sw.starts("CATTUS_WINO_INPLACE", '0');
         p.one_launch = k4 && p.inplace && !sw.starts("CATTUS_WINO_PERSIST", '0');
@@ -1345,7 +1366,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
     else return fail(CATTUS_E_INVALID, "cfg.struct_size mismatch");
     cfg_copy.struct_size = sizeof(cattus_eval_config);
     const cattus_eval_config* cfg = &cfg_copy;
-    if (cfg->tower_form > CATTUS_TOWER_WINOGRAD) return fail(CATTUS_E_INVALID, "unknown tower_form %u", cfg->tower_form);
+    if (cfg->tower_form > CATTUS_TOWER_WINOGRAD_F4) return fail(CATTUS_E_INVALID, "unknown tower_form %u", cfg->tower_form);
     Switches sw;
     if (int src = sw.parse(switches)) return src;
     if (nbytes < HEADER_BYTES || memcmp(weights, "CATTUSW1", 8) != 0) return fail(CATTUS_E_INVALID, "not a cattus weight blob");
@@ -1437,7 +1458,8 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
     if (e->plan.wino() && !sw.starts("CATTUS_ARENA", '0')) {  // CATTUS_ARENA=0: every buffer its own allocation (A/B runs)
         // the Winograd tower's hot set in one block: U of every layer, then the lanes' activation buffers (DevArena)
         auto page = [](size_t b) { return (b + 4095) & ~(size_t)4095; };
-        const size_t FPz = e->fpad, u_bytes = page(((size_t)16 * FPz * FPz * 2 + (size_t)WINO_RING_STAGES * 1024) * 2);
+        const size_t FPz = e->fpad;
+        const size_t u_bytes = page(e->plan.kind == TowerKind::WinoF4 ? winof4_u_elems(e->fpad, e->fpad) * 2 : ((size_t)16 * FPz * FPz * 2 + (size_t)WINO_RING_STAGES * 1024) * 2);
         const size_t act_bytes_ = page((size_t)e->bpad * e->slots * FPz * 4);
         const size_t want = 2 * (size_t)d.blocks * u_bytes + (size_t)NLANES * (e->plan.inplace ? 2 : 3) * act_bytes_ + (1u << 20);
         void* base = nullptr;

@@ -8,6 +8,7 @@
 #include "prior_rule.h"   // PriorRecord and the rule behind it
 #include "legal_span.h"   // the ragged layout of the leaf server's legal-move lists
 #include "tap_layout.h"   // TapSource, TraceRecord: where a point's activations live, the rule of a trace record
+#include "winof4_rule.h"  // the Winograd F(4x4, 3x3) form: matrices, transforms, geometry, cap, U index
 
 namespace cattus {
 
@@ -69,7 +70,9 @@ struct StemInput {
 // flags & CONV_WINO_IN (with CONV_OUT_F32): the rows feed a Winograd tower (K1w): values are capped at WINO_ACT_MAX and counted in
 // `sat` beyond it -- a transformed input B^T d B is a signed sum of four activations, so no |V| can leave the f16 range then and the
 // Winograd kernel's transform needs neither a clamp nor a range check of its own.
-constexpr int CONV_OUT_F32 = 1, CONV_W_FRAG = 2, CONV_WINO_IN = 4;
+// flags & CONV_WINOF4_IN (with CONV_OUT_F32, instead of CONV_WINO_IN): the rows feed a Winograd F(4x4, 3x3) tower (K1f4): the same cap
+// and count at WINOF4_ACT_MAX (winof4_rule.h).
+constexpr int CONV_OUT_F32 = 1, CONV_W_FRAG = 2, CONV_WINO_IN = 4, CONV_WINOF4_IN = 8;
 constexpr float WINO_ACT_MAX = 16376.0f;  // 65504 / 4, exactly
 // Per-evaluator launch options (they used to be process-wide switches: a second evaluator must not re-tile the first).
 struct ConvOpts {
@@ -116,6 +119,16 @@ struct Wino4TowerLayer {
 bool wino4_tower_fits(uint32_t bpad, uint32_t filters, uint32_t cus);
 void launch_tower_wino4(const Wino4TowerLayer* d_layers, uint32_t nlayers, unsigned* ready, unsigned* err, unsigned* sat, uint32_t bpad, uint32_t filters,
                         uint32_t spin_budget, uint32_t cus, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop);
+
+// ---- K1f4: the split-precision conv in Winograd F(4x4, 3x3) form (kernels_winof4.hip; winof4_rule.h has the rule) ----
+// The arguments of launch_conv3x3_wino4: in / res / out plain f32 rows on 64-slot boards, res may be out; wu = G g G^T as (hi, lo) f16
+// pairs pre-scaled per output channel in the order of winof4_frag_index (weight_layout.h: winof4_u; nothing is read past it); bias =
+// [cout biases | cout inverse scales] of that scaling; outputs are capped at WINOF4_ACT_MAX and sat counts the threads that wrote the cap.
+// bpad % 4 == 0: a workgroup takes 8 boards, the last one 4 when bpad is no multiple of 8.
+bool winof4_supported(uint32_t bpad, uint32_t cin, uint32_t cout, uint32_t S);
+void launch_conv3x3_winof4(const float* in, const void* wu, const float* bias, const float* res, float* out, uint32_t bpad, uint32_t cin,
+                           uint32_t cout, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, unsigned* sat);
+hipError_t prepare_winof4();
 
 // ---- calibration: the range of one stream tensor of the f32 per-layer tower (cattus_hip_stream_range) ----
 // rows: plain f32 [nb * slots][FP] (nb * slots % 256 == 0, FP % 64 == 0), of which board < n and pixel slot < S * S are live.  Adds,

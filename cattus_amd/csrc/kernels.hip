@@ -775,6 +775,7 @@ __device__ __forceinline__ void finish_f16x2(const char* rowp, int px, int cg, c
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     if (flags & CONV_OUT_F32) {
         if (flags & CONV_WINO_IN) cap_wino_input(y, valid, sat);
+        else if (flags & CONV_WINOF4_IN) cap_winof4_input(y, valid, sat);
         float* of = reinterpret_cast<float*>(out) + row * (size_t)cout + col;
         const f32x4 y0 = valid ? *reinterpret_cast<f32x4*>(y) : zero4, y1 = valid ? *reinterpret_cast<f32x4*>(y + 4) : zero4;
         if constexpr (CB == 2) {
@@ -1913,7 +1914,7 @@ hipError_t prepare_device() {
     conv_opt_in<ConvSplit>(err);
     conv_opt_in<ConvSplitW>(err);
     for_each_tower64([&](auto kernel, int lds, auto...) { lds_opt_in(err, kernel, lds); });
-    for (hipError_t e : {prepare_tower64_split(), prepare_wino(), prepare_wino4()})
+    for (hipError_t e : {prepare_tower64_split(), prepare_wino(), prepare_wino4(), prepare_winof4()})
         if (err == hipSuccess) err = e;
     return err;
 }

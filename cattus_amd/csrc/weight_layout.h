@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "frag_index.h"
+#include "winof4_rule.h"
 
 namespace cattus {
 
@@ -78,13 +79,16 @@ inline std::vector<int> stream_shifts(const std::vector<double>& s2) {
 // one.  4096 = 2^12 is a quarter of the Winograd form's cap (WINO_ACT_MAX, 16376): a factor of four for positions outside the
 // sample.  The guard stops at 0 -- a stream is never shifted down -- so a guarded t_k can lie below the global shift, which stays
 // stream_shift_global(s2_measured).
+// `headroom`: the F(4x4, 3x3) form passes a quarter of ITS cap (WINOF4_CAL_HEADROOM below).
 constexpr double STREAM_CAL_HEADROOM = 4096.0;
-inline std::vector<int> calibrated_stream_shifts(const std::vector<double>& s2_measured, const std::vector<double>& abs_max) {
+inline std::vector<int> calibrated_stream_shifts(const std::vector<double>& s2_measured, const std::vector<double>& abs_max,
+                                                 double headroom = STREAM_CAL_HEADROOM) {
     std::vector<int> tk = stream_shifts(s2_measured);
     for (size_t k = 0; k < tk.size() && k < abs_max.size(); k++)
-        while (tk[k] > 0 && ldexp(abs_max[k], tk[k]) > STREAM_CAL_HEADROOM) tk[k]--;
+        while (tk[k] > 0 && ldexp(abs_max[k], tk[k]) > headroom) tk[k]--;
     return tk;
 }
+constexpr double WINOF4_CAL_HEADROOM = WINOF4_ACT_MAX / 4;  // 163.75
 
 // [cout_pad biases | cout_pad inverse scales 2^-shift]; without shifts (f32, bf16) the biases alone
 inline std::vector<float> bias_and_scales(const Folded& f, const ConvShape& s, const std::vector<int>* shift = nullptr) {
@@ -176,6 +180,41 @@ inline std::vector<_Float16> wino_u(const std::vector<double>& U, const ConvShap
         for (uint32_t ci = 0; ci < s.cin; ci++)
             for (uint32_t q = 0; q < 16; q++)
                 split_f16((float)ldexp(U[((size_t)co * s.cin + ci) * 16 + q], shift[co]), wu[wino_frag_index(q, co, ci, 0, s.cin_pad)], wu[wino_frag_index(q, co, ci, 1, s.cin_pad)]);
+    return wu;
+}
+
+// Winograd F(4x4, 3x3) form (winof4_rule.h): U = G g G^T per (cout, cin) in float64, [(co * cin + ci) * 36 + frequency], and one scale
+// per output channel over all 36 frequencies of all its input channels
+inline std::vector<double> winof4_transform(const Folded& f, const ConvShape& s, std::vector<int>* shift) {
+    std::vector<double> U((size_t)s.cout * s.cin * WINOF4_FREQ);
+    shift->assign(s.cout_pad, 0);
+    for (uint32_t co = 0; co < s.cout; co++) {
+        double m = 0.0;
+        for (uint32_t ci = 0; ci < s.cin; ci++) {
+            double g[3][3], t[6][3];
+            for (int ky = 0; ky < 3; ky++)
+                for (int kx = 0; kx < 3; kx++) g[ky][kx] = f.w[((size_t)(ky * 3 + kx) * s.cout + co) * s.cin + ci];
+            for (int i = 0; i < 6; i++)
+                for (int kx = 0; kx < 3; kx++) t[i][kx] = WINOF4_G[i][0] * g[0][kx] + WINOF4_G[i][1] * g[1][kx] + WINOF4_G[i][2] * g[2][kx];
+            for (int i = 0; i < 6; i++)
+                for (int l = 0; l < 6; l++) {
+                    const double u = t[i][0] * WINOF4_G[l][0] + t[i][1] * WINOF4_G[l][1] + t[i][2] * WINOF4_G[l][2];
+                    U[((size_t)co * s.cin + ci) * WINOF4_FREQ + i * 6 + l] = u;
+                    m = std::max(m, fabs(u));
+                }
+        }
+        (*shift)[co] = channel_shift(m);
+    }
+    return U;
+}
+// U 2^s as (hi, lo) pairs in the F(4x4) kernel's fragment order (winof4_frag_index); the kernel reads nothing past the payload
+inline std::vector<_Float16> winof4_u(const std::vector<double>& U, const ConvShape& s, const std::vector<int>& shift) {
+    std::vector<_Float16> wu(winof4_u_elems(s.cout_pad, s.cin_pad), (_Float16)0.0f);
+    for (uint32_t co = 0; co < s.cout; co++)
+        for (uint32_t ci = 0; ci < s.cin; ci++)
+            for (uint32_t q = 0; q < (uint32_t)WINOF4_FREQ; q++)
+                split_f16((float)ldexp(U[((size_t)co * s.cin + ci) * WINOF4_FREQ + q], shift[co]), wu[winof4_frag_index(q, co, ci, 0, s.cin_pad)],
+                          wu[winof4_frag_index(q, co, ci, 1, s.cin_pad)]);
     return wu;
 }
 

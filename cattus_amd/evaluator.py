@@ -92,7 +92,7 @@ class EvalConfig(C.Structure):
     ]
 
 
-TOWER_FORMS = {"auto": 0, "direct": 1, "winograd": 2}  # cattus_tower_form
+TOWER_FORMS = {"auto": 0, "direct": 1, "winograd": 2, "winograd_f4": 3}  # cattus_tower_form
 # Diagnostic switches (include/cattus_hip_diag.h).  The library reads none of them from the environment; this binding -- the
 # harness of the tests and the timing scripts -- forwards the ones it finds there through cattus_hip_create_diag, so that
 # `CATTUS_TOWER64=0 python scripts/...` and monkeypatch.setenv keep working.  CATTUS_WINOGRAD=0/1 (rounds 3-4) maps to tower_form.
@@ -320,8 +320,8 @@ class HipEvaluator:
         calibration=None,
         verify_every: int = 0,
     ):
-        """tower_form: "auto" | "direct" | "winograd" (cattus_tower_form; None = "auto", or what CATTUS_WINOGRAD=0/1 in the
-        environment says).  switches: diagnostic switches for cattus_hip_create_diag (None = the CATTUS_* ones found in the
+        """tower_form: "auto" | "direct" | "winograd" | "winograd_f4" (cattus_tower_form; None = "auto", or what CATTUS_WINOGRAD=0/1 in the
+        environment says; "winograd_f4", the F(4x4,3x3) form, is opt-in only: never what "auto" picks).  switches: diagnostic switches for cattus_hip_create_diag (None = the CATTUS_* ones found in the
         environment, {} = none).  calibration: sample positions, uint64 ``[n, C, plane_words]`` -- the f16 / f16x2 towers then
         take their stream shifts from the range measured on them instead of from the BatchNorm parameters
         (cattus_hip_create_calibrated; nothing to calibrate for f32 / bf16, which come out as without it).  verify_every: N >= 1

@@ -59,6 +59,15 @@ typedef enum cattus_tower_form {
     CATTUS_TOWER_AUTO = 0,     /* Winograd where the shape allows it and max_batch > 128, else direct */
     CATTUS_TOWER_DIRECT = 1,   /* direct 3x3 (conv3x3_splitw_kernel): the faster form up to 128 leaves per batch */
     CATTUS_TOWER_WINOGRAD = 2, /* Winograd F(2x2,3x3) whatever max_batch is; CATTUS_E_UNSUPPORTED where no such kernel exists */
+    /* Winograd F(4x4,3x3) (conv3x3_winof4_kernel): 36 products per 4x4 outputs and input channel where F(2x2,3x3) needs 64.  Opt-in:
+     * NEVER chosen by AUTO, always one launch per layer.  Coverage as for WINOGRAD (f16x2, 8x8 board, at least one residual block, a
+     * multiple of 64 filters, at least 128), else CATTUS_E_UNSUPPORTED.  Its bits are its own; on a 20-block network its error against
+     * a float64 run is 2.2-2.8x the direct form's and inside the reference's cross-runtime tolerance (profiles/winograd_gate_f4.json).
+     * The error grows with depth (chess 40x384: 2.7x the direct form's): networks far deeper than 20 blocks may leave that tolerance --
+     * check with cattus_hip_verify.
+     * Range: activations are capped at 655 in stream units -- 25x tighter than the other Winograd form's 16376 -- and a stream is
+     * never shifted DOWN: a network whose activations pass 655 counts in cattus_stats.saturated and belongs on another form. */
+    CATTUS_TOWER_WINOGRAD_F4 = 3,
 } cattus_tower_form;
 
 /* Replaces the reference's InferenceConfig + batch_size (engine/src/net/model.rs:17-25,
@@ -80,7 +89,7 @@ typedef struct cattus_stats {
     double run_seconds_ema; /* == reference metric model.run_duration (EMA 0.99, util/metric.rs:16-19) */
     double run_seconds_total;
     /* f16x2 / f16 towers: activation values that exceeded the f16 range (65504; in the Winograd form of the f16x2 tower a
-     * quarter of it, 16376: its transformed inputs are sums of four) and were clamped, since the evaluator was created (sticky).  0 for every network inside the range; > 0 means outputs of this evaluator are NOT the network's:
+     * quarter of it, 16376: its transformed inputs are sums of four; in the F(4x4,3x3) form 655) and were clamped, since the evaluator was created (sticky).  0 for every network inside the range; > 0 means outputs of this evaluator are NOT the network's:
      * use dtype f32 for that network (a BatchNorm scale of 1e5 does it; one of 200 does not). */
     uint64_t saturated;
 } cattus_stats;

@@ -33,7 +33,8 @@ struct CattusEvalConfig {
     plane_words: u32,
     dtype: u32,
     flush_us: u32,
-    /// cattus_tower_form: 0 = auto (Winograd form of the f16x2 tower for batch_size >= 192), 1 = direct, 2 = Winograd
+    /// cattus_tower_form: 0 = auto (Winograd form of the f16x2 tower for batch_size >= 192), 1 = direct, 2 = Winograd F(2x2,3x3),
+    /// 3 = Winograd F(4x4,3x3) (opt-in, never what auto picks; activations capped at 655: see include/cattus_hip.h)
     tower_form: u32,
 }
 
