@@ -367,6 +367,10 @@ struct cattus_eval {
     // wait) -- that batch is run again on the per-layer launches, and so is every later one
     std::atomic<bool> tower_gave_up{false};
     uint32_t persist_spin = 1u << 18, cus = 0;
+    // cattus_eval_config.tail_leaves as it holds on this plan (0 on every plan but Wino4 / Wino16): an unobserved pass of at most this many
+    // leaves runs the layers behind the stem on the small-tile kernel (kernels_wino4s.hip), the same bits; tail_batches counts those passes
+    uint32_t tail_leaves = 0;
+    std::atomic<uint64_t> tail_batches{0};
     // the f16 towers carry the residual stream at 2^stream_shift times its size, channel k of it at 2^stream_shifts[k] >= that
     // (choose_stream_shift; from cattus_hip_create_calibrated: calibrated_stream_shifts, whose headroom guard can take a channel
     // below the global shift); CATTUS_STREAM_SHIFT=0: never
@@ -864,7 +868,9 @@ struct Forward {
         const bool f4 = e->plan.kind == TowerKind::WinoF4;
         conv_mfma(e->stem, L.x0.p, nullptr, a, CONV_OUT_F32 | (f4 ? CONV_WINOF4_IN : CONV_WINO_IN), true);
         seen(0, a, tower_source(0));
-        if (!obs && one_launch_now(e, nb)) {
+        const bool tail = !obs && e->tail_leaves && n <= e->tail_leaves;  // a short batch: the small-tile kernel, one launch per layer
+        if (tail && !tt) e->tail_batches.fetch_add(1, std::memory_order_relaxed);  // (a timing pass is not a batch)
+        if (!obs && !tail && one_launch_now(e, nb)) {
             // every layer behind the stem in ONE launch: counters and error word zeroed ahead of it on the same stream, the error word
             // copied to page-locked memory behind it (eval_host reads it when the batch is back; the device entry points at their next call)
             hipEvent_t s0 = ev(), s1 = ev();
@@ -878,7 +884,7 @@ struct Forward {
             HIP_TRY(hipMemcpyAsync(L.h_tower_err.p, tower_err, 4, hipMemcpyDeviceToHost, st));
             return CATTUS_OK;
         }
-        const auto launch = f4 ? launch_conv3x3_winof4 : e->plan.kind == TowerKind::Wino4 ? launch_conv3x3_wino4 : launch_conv3x3_wino;
+        const auto launch = f4 ? launch_conv3x3_winof4 : tail ? launch_conv3x3_wino4s : e->plan.kind == TowerKind::Wino4 ? launch_conv3x3_wino4 : launch_conv3x3_wino;
         auto conv = [&](const ConvLayer& c, const float* in, const float* res, float* out) {
             hipEvent_t s0 = ev(), s1 = ev();
             launch(in, c.w.p, c.b.as<float>(), res, out, nb, FP, FP, st, s0, s1, e->conv_opts.saturated);
@@ -1261,6 +1267,18 @@ CATTUS_API const char* cattus_hip_tower_kernel(const cattus_eval* e) {
     return e->act != Act::F16S ? "conv3x3_mfma_v2_kernel" : e->plan.w_frag ? "conv3x3_splitw_kernel" : "conv3x3_split_kernel";
 }
 
+CATTUS_API int cattus_hip_tail_leaves(const cattus_eval* e, uint32_t* effective) {
+    if (!e || !effective) return fail(CATTUS_E_INVALID, "NULL argument");
+    *effective = e->tail_leaves;
+    return CATTUS_OK;
+}
+
+CATTUS_API int cattus_hip_tail_batches(cattus_eval* e, uint64_t* batches) {
+    if (!e || !batches) return fail(CATTUS_E_INVALID, "NULL argument");
+    *batches = e->tail_batches.load(std::memory_order_relaxed);
+    return CATTUS_OK;
+}
+
 CATTUS_API int cattus_hip_stream_shift(const cattus_eval* e) { return e ? e->stream_shift : 0; }
 
 CATTUS_API int cattus_hip_stream_shifts(const cattus_eval* e, int* out, uint32_t n) {
@@ -1355,18 +1373,24 @@ int resolve_plan(const cattus_net_desc& d, const cattus_eval_config& cfg, const 
     return CATTUS_OK;
 }
 
+// the lengths cattus_eval_config has had: up to flush_us, with tower_form, with tail_leaves
+bool config_size_known(uint32_t size) {
+    return size == offsetof(cattus_eval_config, tower_form) || size == offsetof(cattus_eval_config, tail_leaves) || size == sizeof(cattus_eval_config);
+}
+
 int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cfg_in, const char* switches, cattus_eval** out, const Calibration* cal = nullptr) {
     if (!out) return fail(CATTUS_E_INVALID, "out is NULL");
     *out = nullptr;
     if (!weights || !cfg_in) return fail(CATTUS_E_INVALID, "weights/cfg is NULL");
-    // struct_size versions the configuration: 24 bytes = the fields up to flush_us (tower_form = AUTO), 28 = with tower_form
+    // struct_size versions the configuration: 24 bytes = the fields up to flush_us (tower_form = AUTO), 28 = with tower_form (tail_leaves = 0),
+    // 32 = with tail_leaves
     cattus_eval_config cfg_copy{};
-    if (cfg_in->struct_size == offsetof(cattus_eval_config, tower_form)) memcpy(&cfg_copy, cfg_in, offsetof(cattus_eval_config, tower_form));
-    else if (cfg_in->struct_size == sizeof(cattus_eval_config)) cfg_copy = *cfg_in;
-    else return fail(CATTUS_E_INVALID, "cfg.struct_size mismatch");
+    if (!config_size_known(cfg_in->struct_size)) return fail(CATTUS_E_INVALID, "cfg.struct_size mismatch");
+    memcpy(&cfg_copy, cfg_in, cfg_in->struct_size);
     cfg_copy.struct_size = sizeof(cattus_eval_config);
     const cattus_eval_config* cfg = &cfg_copy;
     if (cfg->tower_form > CATTUS_TOWER_WINOGRAD_F4) return fail(CATTUS_E_INVALID, "unknown tower_form %u", cfg->tower_form);
+    if (cfg->tail_leaves > cfg->max_batch) return fail(CATTUS_E_INVALID, "tail_leaves %u is more than max_batch %u", cfg->tail_leaves, cfg->max_batch);
     Switches sw;
     if (int src = sw.parse(switches)) return src;
     if (nbytes < HEADER_BYTES || memcmp(weights, "CATTUSW1", 8) != 0) return fail(CATTUS_E_INVALID, "not a cattus weight blob");
@@ -1446,6 +1470,9 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
     e->fpad = (d.filters + COUT_PER_WG - 1) / COUT_PER_WG * COUT_PER_WG;
     if (int prc = resolve_plan(d, *cfg, sw, e->act, e->bpad, e->fpad, e->cpad0, &e->plan)) return prc;
     if (!e->plan.tuned()) e->bpad = cfg->max_batch, e->fpad = d.filters, e->cpad0 = d.planes;
+    // short batches on the small-tile kernel: only where the plan is the F(2x2) Winograd tower (the kernel computes that tower's bits and no
+    // other's) and the kernel covers the layer shape; everywhere else the field is ignored
+    if ((e->plan.kind == TowerKind::Wino4 || e->plan.kind == TowerKind::Wino16) && wino4_supported(e->bpad, e->fpad, e->fpad, d.board)) e->tail_leaves = cfg->tail_leaves;
     if (act_f16_family(e->act)) {
         if (int src = e->d_saturated.alloc(sizeof(unsigned))) return src;
         HIP_TRY(hipMemset(e->d_saturated.p, 0, sizeof(unsigned)));
@@ -1541,8 +1568,7 @@ int create_calibrated_impl(const void* weights, size_t nbytes, const cattus_eval
     *out = nullptr;
     if (!weights || !cfg || !planes) return fail(CATTUS_E_INVALID, "weights/cfg/planes is NULL");
     if (n < 1) return fail(CATTUS_E_INVALID, "calibration needs at least one leaf");
-    if (cfg->struct_size != offsetof(cattus_eval_config, tower_form) && cfg->struct_size != sizeof(cattus_eval_config))
-        return fail(CATTUS_E_INVALID, "cfg.struct_size mismatch");
+    if (!config_size_known(cfg->struct_size)) return fail(CATTUS_E_INVALID, "cfg.struct_size mismatch");
     uint32_t filters = 0;  // 0: SimpleTwoHeadedModel (or no blob at all, which create_impl refuses)
     if (nbytes >= HEADER_BYTES) memcpy(&filters, (const char*)weights + 8 + 5 * 4, 4);
     // only the f16 towers shift their stream: everything else is cattus_hip_create
@@ -1862,7 +1888,7 @@ int ensure_shadow(cattus_eval* e, const void* weights, size_t nbytes) {
     if (e->shadow) return CATTUS_OK;
     HIP_TRY(hipSetDevice(e->device));
     cattus_eval_config scfg = e->cfg;
-    scfg.dtype = CATTUS_DTYPE_F32, scfg.tower_form = CATTUS_TOWER_AUTO;
+    scfg.dtype = CATTUS_DTYPE_F32, scfg.tower_form = CATTUS_TOWER_AUTO, scfg.tail_leaves = 0;
     return create_impl(weights, nbytes, &scfg, nullptr, &e->shadow);  // CATTUS_E_NOMEM where it does not fit
 }
 

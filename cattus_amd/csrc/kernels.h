@@ -120,6 +120,13 @@ bool wino4_tower_fits(uint32_t bpad, uint32_t filters, uint32_t cus);
 void launch_tower_wino4(const Wino4TowerLayer* d_layers, uint32_t nlayers, unsigned* ready, unsigned* err, unsigned* sat, uint32_t bpad, uint32_t filters,
                         uint32_t spin_budget, uint32_t cus, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop);
 
+// ---- K1w4s: the same layer on a small tile, for short batches (kernels_wino4s.hip; wino4s_rule.h has its geometry and LDS plan) ----
+// Same arguments, same U buffer, same bits as launch_conv3x3_wino4 wherever wino4_supported holds; workgroup = 2 boards x 32 couts, grid
+// (bpad / 2) x (cout / 32), one launch per layer, no cross-workgroup synchronisation.  Nothing is read past U's last stage or the rows.
+void launch_conv3x3_wino4s(const float* in, const void* wu, const float* bias, const float* res, float* out, uint32_t bpad, uint32_t cin,
+                           uint32_t cout, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, unsigned* sat);
+hipError_t prepare_wino4s();
+
 // ---- K1f4: the split-precision conv in Winograd F(4x4, 3x3) form (kernels_winof4.hip; winof4_rule.h has the rule) ----
 // The arguments of launch_conv3x3_wino4: in / res / out plain f32 rows on 64-slot boards, res may be out; wu = G g G^T as (hi, lo) f16
 // pairs pre-scaled per output channel in the order of winof4_frag_index (weight_layout.h: winof4_u; nothing is read past it); bias =

@@ -1914,7 +1914,7 @@ hipError_t prepare_device() {
     conv_opt_in<ConvSplit>(err);
     conv_opt_in<ConvSplitW>(err);
     for_each_tower64([&](auto kernel, int lds, auto...) { lds_opt_in(err, kernel, lds); });
-    for (hipError_t e : {prepare_tower64_split(), prepare_wino(), prepare_wino4(), prepare_winof4()})
+    for (hipError_t e : {prepare_tower64_split(), prepare_wino(), prepare_wino4(), prepare_winof4(), prepare_wino4s()})
         if (err == hipSuccess) err = e;
     return err;
 }

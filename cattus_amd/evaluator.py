@@ -54,6 +54,8 @@ ABI_SYMBOLS = [
     "cattus_hip_version",
     "cattus_hip_runtime_note",
     "cattus_hip_tower_kernel",
+    "cattus_hip_tail_leaves",
+    "cattus_hip_tail_batches",
     "cattus_hip_stream_range",
     "cattus_hip_create_calibrated",
     "cattus_hip_verify",
@@ -89,6 +91,7 @@ class EvalConfig(C.Structure):
         ("dtype", C.c_uint32),
         ("flush_us", C.c_uint32),
         ("tower_form", C.c_uint32),
+        ("tail_leaves", C.c_uint32),
     ]
 
 
@@ -224,6 +227,8 @@ def load_library():
     L.cattus_hip_runtime_note.restype = C.c_char_p
     L.cattus_hip_tower_kernel.argtypes = [vp]
     L.cattus_hip_tower_kernel.restype = C.c_char_p
+    L.cattus_hip_tail_leaves.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.cattus_hip_tail_batches.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.cattus_hip_stream_shift.argtypes = [vp]
     L.cattus_hip_stream_shifts.argtypes = [vp, C.POINTER(C.c_int), C.c_uint32]
     L.cattus_hip_stem_input.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -319,13 +324,16 @@ class HipEvaluator:
         switches: dict | None = None,
         calibration=None,
         verify_every: int = 0,
+        tail_leaves: int = 0,
     ):
         """tower_form: "auto" | "direct" | "winograd" | "winograd_f4" (cattus_tower_form; None = "auto", or what CATTUS_WINOGRAD=0/1 in the
         environment says; "winograd_f4", the F(4x4,3x3) form, is opt-in only: never what "auto" picks).  switches: diagnostic switches for cattus_hip_create_diag (None = the CATTUS_* ones found in the
         environment, {} = none).  calibration: sample positions, uint64 ``[n, C, plane_words]`` -- the f16 / f16x2 towers then
         take their stream shifts from the range measured on them instead of from the BatchNorm parameters
         (cattus_hip_create_calibrated; nothing to calibrate for f32 / bf16, which come out as without it).  verify_every: N >= 1
-        checks every Nth batch against a shadow f32 tower (``verify``); 0, the default, builds no shadow and checks nothing."""
+        checks every Nth batch against a shadow f32 tower (``verify``); 0, the default, builds no shadow and checks nothing.
+        tail_leaves: k >= 1 runs batches of at most k leaves of the Winograd F(2x2,3x3) tower on its small-tile kernel (cattus_eval_config.tail_leaves:
+        the same bits, more workgroups for a short batch); ignored on every other plan (``tail_leaves()`` says what holds); 0, the default: off."""
         self.desc: NetDesc = parse_header(blob)
         self.batch_size = int(batch_size)
         self.plane_words = int(plane_words)
@@ -341,7 +349,7 @@ class HipEvaluator:
         if switches is None:
             switches = {k: os.environ[k] for k in DIAG_SWITCHES if k in os.environ}
         self.tower_form = tower_form
-        cfg = EvalConfig(C.sizeof(EvalConfig), device, self.batch_size, self.plane_words, _DTYPES[dtype], flush_us, TOWER_FORMS[tower_form])
+        cfg = EvalConfig(C.sizeof(EvalConfig), device, self.batch_size, self.plane_words, _DTYPES[dtype], flush_us, TOWER_FORMS[tower_form], int(tail_leaves))
         h = C.c_void_p()
         buf = C.create_string_buffer(blob, len(blob))
         text = ";".join(f"{k}={v}" for k, v in switches.items()).encode() if switches else None
@@ -628,6 +636,18 @@ class HipEvaluator:
         t = C.c_double()
         _check(self._lib.cattus_hip_mfma_sustained(self._h, float(seconds), C.byref(t)))
         return t.value
+
+    def tail_leaves(self) -> int:
+        """``tail_leaves`` as it holds for this evaluator: what it was created with on a Winograd F(2x2,3x3) plan, 0 on every other."""
+        k = C.c_uint32()
+        _check(self._lib.cattus_hip_tail_leaves(self._h, C.byref(k)))
+        return k.value
+
+    def tail_batches(self) -> int:
+        """Batches that took the short path (at most ``tail_leaves()`` leaves) since the evaluator was created."""
+        k = C.c_uint64()
+        _check(self._lib.cattus_hip_tail_batches(self._h, C.byref(k)))
+        return k.value
 
     def time_tower(self, n: int, reps: int) -> tuple[float, int]:
         """(average device microseconds of one tower conv launch, launches per forward)."""

@@ -624,11 +624,14 @@ def main(argv=None):
     verify_every = int(inf.get("verify_every", 0))
     # optional: calc_moves_probs on the device (cattus_hip_eval_legal; Net.hip(..., device_softmax=True)); absent or false: on the host
     device_softmax = bool(inf.get("device_softmax", False))
+    # optional: batches of at most this many leaves on the Winograd tower's small-tile kernel (cattus_eval_config.tail_leaves: the same bits);
+    # absent or 0: off
+    tail_leaves = int(inf.get("tail_leaves", 0))
 
     def load(path):
         blob = Path(path).read_bytes()
         return HipEvaluator(blob, batch_size=engine["model"]["batch_size"], plane_words=info["plane_words"],
-                            dtype=inf.get("dtype", "f16x2"), device=inf.get("device", 0), verify_every=verify_every)
+                            dtype=inf.get("dtype", "f16x2"), device=inf.get("device", 0), verify_every=verify_every, tail_leaves=tail_leaves)
 
     ev1 = load(args.model1_path)
     same = os.path.abspath(args.model1_path) == os.path.abspath(args.model2_path)

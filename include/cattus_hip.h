@@ -73,13 +73,30 @@ typedef enum cattus_tower_form {
 /* Replaces the reference's InferenceConfig + batch_size (engine/src/net/model.rs:17-25,
  * training/self-play/src/self_play_cmd.rs:41-44). */
 typedef struct cattus_eval_config {
-    uint32_t struct_size; /* sizeof(cattus_eval_config); 24 (the fields up to flush_us, tower_form = AUTO) is accepted too */
+    /* sizeof(cattus_eval_config) = 32.  The earlier lengths are accepted too: 24 (the fields up to flush_us: tower_form = AUTO) and
+     * 28 (up to tower_form); both mean tail_leaves = 0. */
+    uint32_t struct_size;
     int32_t device;       /* HIP device ordinal */
     uint32_t max_batch;   /* model.batch_size: largest n accepted by eval / batch the server fills */
     uint32_t plane_words; /* u64 words per bitboard plane: chess 1, ttt 1, hex 2 (u128 as lo,hi) */
     uint32_t dtype;       /* cattus_dtype */
     uint32_t flush_us;    /* partial-batch deadline of the leaf server (reference: 20 ms, net/mod.rs:96) */
     uint32_t tower_form;  /* cattus_tower_form; ignored by every dtype but f16x2 */
+    /* Short batches of the Winograd F(2x2,3x3) tower (f16x2, AUTO with max_batch > 128 or WINOGRAD).  0, the default: nothing changes.
+     * k > 0: a batch of n <= k leaves runs the layers behind the stem on conv3x3_wino4s_kernel, a kernel for the same arithmetic whose
+     * workgroup takes 2 boards x 32 output channels where the tower's takes 4 x 64 -- four times as many workgroups for a batch that
+     * leaves most of the chip idle.  THE BITS DO NOT CHANGE: every logit and value equals, bit for bit, what the evaluator returns with
+     * tail_leaves = 0, for every n and every k, so a leaf's result still does not depend on the batch it came in
+     * (tests/test_short_batches_gpu.py).  Ignored (cattus_hip_tail_leaves reports 0) on every other plan: the direct form, f32 / bf16 /
+     * f16, WINOGRAD_F4, networks of <= 64 filters.  k > max_batch is CATTUS_E_INVALID.
+     * Measured (whole step through cattus_hip_eval_device, default | tail_leaves = n, ms; scripts/short_batch_time.py ->
+     * profiles/wino_short_batches.txt), chess 20x256:  1 leaf 0.894 | 0.760,  8: 0.896 | 0.768,  16: 0.893 | 0.779,  32: 0.892 | 0.786,
+     * 64: 0.894 | 0.799,  96: 0.898 | 1.482,  128: 0.902 | 1.501;  chess 4x128: 0.145 | 0.108 at 1 leaf ... 0.145 | 0.118 at 128.
+     * Against the 12 % by which two boxes differ on one binary that makes it RECOMMENDED UP TO 16 LEAVES ON 256 FILTERS (13-15 % faster;
+     * at 32 and 64 it is 12 % and 11 % faster, inside that spread) and up to 128 on 128 filters (18-25 % faster).  From the batch whose
+     * grid passes the device's 256 CUs on (more than 64 leaves on 256 filters) it is 1.65x SLOWER: never set it above
+     * 64 * 256 / filters.  The default stays 0. */
+    uint32_t tail_leaves;
 } cattus_eval_config;
 
 typedef struct cattus_stats {
@@ -372,6 +389,13 @@ int cattus_hip_planes_to_tensor_device(const uint64_t* d_planes, uint32_t n, uin
  * "tower_wino4_kernel" (f16x2 on 8x8 boards with max_batch > 128: the Winograd tower, every layer behind the stem in one launch),
  * "tower64_split_kernel", "conv3x3_mfma_v2_kernel", ... */
 const char* cattus_hip_tower_kernel(const cattus_eval* e);
+
+/* cattus_eval_config.tail_leaves as it holds for this evaluator: the configured value on a Winograd F(2x2,3x3) plan, 0 on every other
+ * (the field is ignored there).  cattus_hip_tower_kernel keeps naming the plan's kernel. */
+int cattus_hip_tail_leaves(const cattus_eval* e, uint32_t* effective);
+/* Batches that took the short path (n <= tail_leaves, not observed by tap / trace) since the evaluator was created, through any entry
+ * point; a timing pass of cattus_hip_time_tower is not a batch. */
+int cattus_hip_tail_batches(cattus_eval* e, uint64_t* batches);
 
 const char* cattus_hip_last_error(void);
 const char* cattus_hip_version(void);

@@ -8,7 +8,7 @@
 //! Drop this file next to `model.rs`, apply `cattus_hip.patch`, build with `--features hip` and
 //! `CATTUS_HIP_LIB_DIR=<repo>/cattus_amd`.
 
-use std::ffi::{c_char, c_void, CStr};
+use std::ffi::{c_char, c_uint, c_void, CStr};
 use std::path::Path;
 
 /// `cattus_dtype` of include/cattus_hip.h
@@ -36,6 +36,9 @@ struct CattusEvalConfig {
     /// cattus_tower_form: 0 = auto (Winograd form of the f16x2 tower for batch_size >= 192), 1 = direct, 2 = Winograd F(2x2,3x3),
     /// 3 = Winograd F(4x4,3x3) (opt-in, never what auto picks; activations capped at 655: see include/cattus_hip.h)
     tower_form: u32,
+    /// batches of at most this many leaves of the Winograd F(2x2,3x3) tower run on its small-tile kernel: the same bits, more workgroups
+    /// for a short batch; 0 = off; ignored on every other plan (uint32_t tail_leaves of include/cattus_hip.h)
+    tail_leaves: c_uint,
 }
 
 #[repr(C)]
@@ -88,6 +91,14 @@ impl HipModel {
     /// `path`: the weight blob `cattus_amd.weights.blob_from_state_dict` writes from `model.pt` (`model.cattus`).
     /// `planes` = planes per position, `plane_words` = `Bitboard::PLANE_WORDS`, `moves` = `Game::MOVES_NUM`.
     pub fn new(path: impl AsRef<Path>, batch_size: usize, planes: usize, plane_words: usize, moves: usize, device: i32, dtype: HipDtype) -> Self {
+        Self::with_tail_leaves(path, batch_size, planes, plane_words, moves, device, dtype, 0)
+    }
+
+    /// `new` with `cattus_eval_config.tail_leaves`: batches of at most `tail_leaves` leaves (<= `batch_size`) take the Winograd tower's
+    /// small-tile kernel.  Every logit and value keeps its bits; see include/cattus_hip.h for where it pays.
+    #[allow(clippy::too_many_arguments)]
+    pub fn with_tail_leaves(path: impl AsRef<Path>, batch_size: usize, planes: usize, plane_words: usize, moves: usize, device: i32, dtype: HipDtype,
+                            tail_leaves: u32) -> Self {
         let blob = std::fs::read(path.as_ref()).unwrap();
         let cfg = CattusEvalConfig {
             struct_size: std::mem::size_of::<CattusEvalConfig>() as u32,
@@ -98,6 +109,7 @@ impl HipModel {
             // partial batches run after 200 us (the reference's Batcher waits 20 ms: net/mod.rs:96)
             flush_us: 200,
             tower_form: 0,
+            tail_leaves,
         };
         let mut h = std::ptr::null_mut();
         check(unsafe { cattus_hip_create(blob.as_ptr().cast(), blob.len(), &cfg, &mut h) });

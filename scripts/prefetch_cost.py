@@ -38,6 +38,7 @@ ap.add_argument("--threads", type=int, default=max(1, min(16, sp.available_cpus(
 ap.add_argument("--blocks", type=int, default=20)
 ap.add_argument("--filters", type=int, default=256)
 ap.add_argument("--shapes", default="a,b,c")
+ap.add_argument("--tail-leaves", type=int, default=0, help="cattus_eval_config.tail_leaves of the evaluators (capped at their max_batch; ignored on the direct plan)")
 ap.add_argument("--out")
 args = ap.parse_args()
 
@@ -49,8 +50,8 @@ SHAPES = {"a": [("a", 64, 64, 0)], "b": [("b", 64, 256, 128)], "c": [("c/32", 8,
 rows, records = [], {}
 for key in args.shapes.split(","):
     for name, games, max_batch, fill in SHAPES[key]:
-        with HipEvaluator(blob, batch_size=max_batch, plane_words=1, dtype="f16x2") as ev:
-            kernel = ev.tower_kernel()
+        with HipEvaluator(blob, batch_size=max_batch, plane_words=1, dtype="f16x2", tail_leaves=min(args.tail_leaves, max_batch)) as ev:
+            kernel = ev.tower_kernel() + ("+tail%d" % ev.tail_leaves() if ev.tail_leaves() else "")
             for rep in range(args.repeats):
                 for k in settings:
                     cfg = sp.make_config(sim_num=args.sims, batch_size=max_batch, max_game_plies=args.plies, threads=args.threads, concurrent_games=games,
@@ -77,9 +78,9 @@ lines = ["command: python scripts/prefetch_cost.py " + " ".join(sys.argv[1:]), "
          "chess %dx%d, f16x2, %d sims, games cut at %d plies, temperature 1.0 / noise 0.03 0.25, %d worker threads, 2 batches in flight, cache 1000000; "
          "settings alternate in one process per shape; the records of every run of a shape are byte-identical (checked)" % (args.blocks, args.filters, args.sims, args.plies, args.threads),
          "evals/s: real leaves per second (speculative rows are not in it); fill: real leaves per batch; rows: real + speculative per batch; hit rate: hits / speculative rows",
-         "%-6s %-22s %-8s %-5s %-9s %-8s %-6s %-6s %-10s %-8s %-8s %-8s %s" % ("shape", "kernel", "prefetch", "fill", "evals/s", "batches", "fill", "rows", "spec_rows", "hits", "hit_rate", "plies/s", "seconds")]
+         "%-6s %-28s %-8s %-5s %-9s %-8s %-6s %-6s %-10s %-8s %-8s %-8s %s" % ("shape", "kernel", "prefetch", "fill", "evals/s", "batches", "fill", "rows", "spec_rows", "hits", "hit_rate", "plies/s", "seconds")]
 for r in rows:
-    lines.append("%-6s %-22s %-8d %-5d %-9.0f %-8d %-6.1f %-6.1f %-10d %-8d %-8.2f %-8.2f %.2f" % (r["shape"], r["kernel"], r["prefetch"], r["fill"], r["evals_per_s"], r["batches"],
+    lines.append("%-6s %-28s %-8d %-5d %-9.0f %-8d %-6.1f %-6.1f %-10d %-8d %-8.2f %-8.2f %.2f" % (r["shape"], r["kernel"], r["prefetch"], r["fill"], r["evals_per_s"], r["batches"],
                                                                                              r["real_fill"], r["rows_fill"], r["spec_rows"], r["hits"], r["hit_rate"], r["plies_per_s"], r["seconds"]))
 best = {}
 for r in rows:
