@@ -109,7 +109,9 @@ Folded fold_conv(const float* w, uint32_t cout, uint32_t cin, uint32_t taps, con
 // the same bits again) and where s_k is 0 (a dead channel) or not finite; a smaller channel is lifted into [1, 2) as S is, t_k at most
 // 16.  The rule itself is weight_layout.h's stream_shifts (tests/weight_layout_check.cpp); t is what cattus_hip_stream_shift reports,
 // every t_k what cattus_hip_stream_shifts does.
-std::vector<int> choose_stream_shift(const cattus_net_desc& d, const float* p, int* t) {
+// `ceiling` (weight_layout.h, stream_shifts): the F(4x4, 3x3) tower alone passes one, WINOF4_STREAM_CEILING -- a median far below a few
+// channels would carry those past its cap of 655 -- and a channel it holds back has t_k below the t reported here.
+std::vector<int> choose_stream_shift(const cattus_net_desc& d, const float* p, int* t, double ceiling) {
     const uint32_t F = d.filters;
     const float* g0 = p + (size_t)F * d.planes * 9;
     const float* b0 = g0 + F;
@@ -122,7 +124,7 @@ std::vector<int> choose_stream_shift(const cattus_net_desc& d, const float* p, i
         for (uint32_t c = 0; c < F; c++) s[c] += (double)g2[c] * g2[c] + (double)b2[c] * b2[c];
     }
     *t = stream_shift_global(s);
-    return stream_shifts(s);
+    return stream_shifts(s, ceiling);
 }
 
 // What cattus_hip_create_calibrated measured on its sample positions (cattus_hip_stream_range of an f32 evaluator of the same blob): per
@@ -373,7 +375,7 @@ struct cattus_eval {
     std::atomic<uint64_t> tail_batches{0};
     // the f16 towers carry the residual stream at 2^stream_shift times its size, channel k of it at 2^stream_shifts[k] >= that
     // (choose_stream_shift; from cattus_hip_create_calibrated: calibrated_stream_shifts, whose headroom guard can take a channel
-    // below the global shift); CATTUS_STREAM_SHIFT=0: never
+    // below the global shift, as the F(4x4) tower's ceiling on the estimate can); CATTUS_STREAM_SHIFT=0: never
     bool stream_shift_on = true;
     int stream_shift = 0;
     std::vector<int> stream_shifts;
@@ -569,7 +571,7 @@ int build(cattus_eval* e, const float* p, const Calibration* cal) {
         // (the F(4x4) form's cap is 25x tighter: its headroom is a quarter of that cap, as the default is of the F(2x2) form's)
         const double headroom = plan.kind == TowerKind::WinoF4 ? WINOF4_CAL_HEADROOM : STREAM_CAL_HEADROOM;
         if (cal) e->stream_shifts = calibrated_stream_shifts(cal->s2, cal->abs_max, headroom), e->stream_shift = stream_shift_global(cal->s2);
-        else e->stream_shifts = choose_stream_shift(d, p, &e->stream_shift);
+        else e->stream_shifts = choose_stream_shift(d, p, &e->stream_shift, plan.kind == TowerKind::WinoF4 ? WINOF4_STREAM_CEILING : STREAM_NO_CEILING);
     }
     const std::vector<int>& tk = e->stream_shifts;
     const bool shifted = std::any_of(tk.begin(), tk.end(), [](int t) { return t != 0; });

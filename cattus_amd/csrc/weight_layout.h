@@ -65,10 +65,21 @@ inline int stream_shift_channel(double s2_k, int t) {
     if (!(s > 0.0) || !std::isfinite(s) || ldexp(s, t) >= 0.5) return t;
     return std::min(STREAM_SHIFT_MAX, -ilogb(s));  // = t - floor(log2(s 2^t)) > t
 }
-inline std::vector<int> stream_shifts(const std::vector<double>& s2) {
+// `ceiling`: the rule above lifts a channel below the median and never holds back one far above it -- a median at 2^-8 beside channels at 1
+// carries those at 2^8.  The direct form (f16 range 65,504) and the F(2x2) form (cap 16,376) have the room; the F(4x4) form, capped at 655,
+// does not, so the estimate path passes it a ceiling (WINOF4_STREAM_CEILING below): while t_k > 0 and s_k 2^t_k >= ceiling, t_k drops
+// by one.  The guard stops at 0 -- a stream is never shifted down -- so a guarded t_k can lie below the global shift, which stays
+// stream_shift_global(s2).  A dead channel (s_k = 0) and one whose s_k is not finite keep the global shift, as they do above.  The
+// default is no ceiling: every shift as it was (a finite s_k 2^16 is a finite double, never >= infinity).
+constexpr double STREAM_NO_CEILING = HUGE_VAL;
+inline std::vector<int> stream_shifts(const std::vector<double>& s2, double ceiling = STREAM_NO_CEILING) {
     const int t = stream_shift_global(s2);
     std::vector<int> tk(s2.size());
-    for (size_t k = 0; k < s2.size(); k++) tk[k] = stream_shift_channel(s2[k], t);
+    for (size_t k = 0; k < s2.size(); k++) {
+        tk[k] = stream_shift_channel(s2[k], t);
+        const double s = std::sqrt(s2[k]);
+        while (tk[k] > 0 && std::isfinite(s) && ldexp(s, tk[k]) >= ceiling) tk[k]--;
+    }
     return tk;
 }
 
@@ -89,6 +100,14 @@ inline std::vector<int> calibrated_stream_shifts(const std::vector<double>& s2_m
     return tk;
 }
 constexpr double WINOF4_CAL_HEADROOM = WINOF4_ACT_MAX / 4;  // 163.75
+// The F(4x4, 3x3) form's ceiling on the estimate path (stream_shifts' `ceiling`), where there is no abs_max to guard with.  2: a
+// held-back channel ends with s_k 2^t_k in [1, 2) -- the point the lift rule aims at from below -- or at t_k = 0, its own size.  The
+// estimate s_k stands for the channel's RMS; in float64 a channel's largest |value| is at most 3.4x its s_k on the seeded chess 2x128
+// and 2x256 networks (median 1.5x, RMS 0.3x), so a channel held under 2 runs below 7 -- the guarded M8 twins of
+// tests/test_winof4_range_gpu.py measure 4.8 and 4.3 where they ran at 864 and 986 -- of the 163.75 that calibration itself would
+// allow (WINOF4_CAL_HEADROOM) and of the cap's 655: a factor of 24 and of 96 for what the estimate cannot see.  Every seeded network
+// has t = 0, where the guard cannot act: the form's bits on them are what they were.
+constexpr double WINOF4_STREAM_CEILING = 2.0;
 
 // [cout_pad biases | cout_pad inverse scales 2^-shift]; without shifts (f32, bf16) the biases alone
 inline std::vector<float> bias_and_scales(const Folded& f, const ConvShape& s, const std::vector<int>* shift = nullptr) {

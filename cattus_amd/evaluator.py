@@ -607,8 +607,9 @@ class HipEvaluator:
         return self._lib.cattus_hip_stream_shift(self._h)
 
     def stream_shifts(self) -> np.ndarray:
-        """t_k per stream channel (filters entries, each >= stream_shift() unless calibration's headroom guard lowered it;
-        include/cattus_hip_diag.h)."""
+        """t_k per stream channel (filters entries, each >= stream_shift() unless calibration's headroom guard lowered it, or -- under
+        tower_form="winograd_f4", whose activations are capped at 655 -- the estimate's ceiling held back a channel far above the
+        median: t_k then lies below stream_shift(), never below 0; include/cattus_hip_diag.h)."""
         out = np.zeros(self.desc.filters, dtype=np.intc)
         _check(self._lib.cattus_hip_stream_shifts(self._h, out.ctypes.data_as(C.POINTER(C.c_int)), len(out)))
         return out

@@ -47,7 +47,9 @@ int cattus_hip_stream_shift(const cattus_eval* e);
 /* The same per channel: out[k] = t_k >= t, n = the network's filters (anything else: CATTUS_E_INVALID).  Channel k of the stream is
  * carried at 2^t_k times its size; t_k > t where channel k alone is small beside the median one (weight_layout.h, stream_shifts).
  * All 0 wherever cattus_hip_stream_shift is 0 by dtype or switch.  Calibrated: weight_layout.h, calibrated_stream_shifts -- measured
- * channels, and a headroom guard that may take a t_k below t (never below 0). */
+ * channels, and a headroom guard that may take a t_k below t (never below 0).  The F(4x4, 3x3) tower (tower_form WINOGRAD_F4), whose
+ * activations are capped at 655, also holds back on the estimate: a channel far above the median gets t_k < t, down to 0, so that its
+ * estimated size times 2^t_k stays below 2 (weight_layout.h, stream_shifts' ceiling). */
 int cattus_hip_stream_shifts(const cattus_eval* e, int* out, uint32_t n);
 
 /* How the stem conv gets its input.  *channels: its input channels as laid out on the device (the planes padded with zero channels;

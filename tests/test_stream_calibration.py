@@ -51,20 +51,21 @@ def global_shift_restated(s2) -> int:
     return min(STREAM_SHIFT_MAX, -_ilogb(S))
 
 
-def calibrated_shifts_restated(rms, abs_max) -> tuple[int, np.ndarray]:
-    """(global shift, t_k per channel) of calibrated_stream_shifts on s2 = rms^2 in float64 (rms, abs_max: what stream_range returns)."""
+def calibrated_shifts_restated(rms, abs_max, headroom: float = HEADROOM) -> tuple[int, np.ndarray]:
+    """(global shift, t_k per channel) of calibrated_stream_shifts on s2 = rms^2 in float64 (rms, abs_max: what stream_range returns).
+    headroom: the guard's bound, 4096 unless the tower is the F(4x4, 3x3) form (163.75, test_winof4_range_gpu.py)."""
     rms, abs_max = np.asarray(rms, dtype=np.float64), np.asarray(abs_max, dtype=np.float64)
-    return shifts_of_s2(rms * rms, abs_max)
+    return shifts_of_s2(rms * rms, abs_max, headroom)
 
 
-def shifts_of_s2(s2, abs_max) -> tuple[int, np.ndarray]:
+def shifts_of_s2(s2, abs_max, headroom: float = HEADROOM) -> tuple[int, np.ndarray]:
     glob = global_shift_restated(s2)
     out = []
     for s2k, mx in zip(s2, abs_max):
         s = math.sqrt(s2k)
         stays = not (s > 0 and math.isfinite(s)) or math.ldexp(s, glob) >= 0.5
         t = glob if stays else min(STREAM_SHIFT_MAX, -_ilogb(s))
-        while t > 0 and mx * 2.0**t > HEADROOM:
+        while t > 0 and mx * 2.0**t > headroom:
             t -= 1
         out.append(t)
     return glob, np.array(out, dtype=np.int64)

@@ -6,7 +6,10 @@ conv3x3_winof4_kernel, the evaluator's upload and cattus_hip_create_calibrated s
 
 In the program itself: tile geometry (every board pixel the output of exactly one (tile, y, x); off-board patch pixels exactly those
 outside 0..7), the frequency -> wave map, the U index as a bijection onto the payload, winof4_u decoding to the float64 U, the cap's
-derivation.  Against numpy here: the algebra in float64, the f32 transforms bit for bit, calibrated_stream_shifts' default."""
+derivation.  Against numpy here: the algebra in float64, the f32 transforms bit for bit, calibrated_stream_shifts' default, and stream_shifts' ceiling (the guard the F(4x4) tower puts on the
+estimate: a channel far above the median is held back, weight_layout.h WINOF4_STREAM_CEILING) -- dead, infinite and NaN channels, a
+global shift of 16, a channel exactly at the ceiling, a random sweep; guarded_shifts is the restatement test_winof4_range_gpu.py
+holds the evaluator to."""
 
 import math
 import subprocess
@@ -90,7 +93,27 @@ def shifts(s2, abs_max, headroom):
     return out
 
 
-# ---------------------------------------------------------------------------------------- the test
+CEILING = 2.0  # WINOF4_STREAM_CEILING (the program checks the header's constant against this figure)
+
+
+def guarded_shifts(s2, ceiling):
+    """weight_layout.h: stream_shifts with a ceiling -- (global shift, the unguarded t_k, the guarded t_k).  The unguarded rule, then:
+    while t_k > 0 and s_k 2^t_k >= ceiling, t_k drops by one; a dead channel and one whose s_k is not finite keep the global shift."""
+    plain = shifts(list(s2), [0.0] * len(s2), math.inf)  # abs_max 0: the headroom guard of `shifts` never acts
+    srt = sorted(s2)
+    n = len(s2)
+    S = math.sqrt(srt[n // 2] if n % 2 else 0.5 * (srt[n // 2 - 1] + srt[n // 2]))
+    t = 0 if not (S > 0.0) or not math.isfinite(S) or S >= 0.5 else min(16, -math.frexp(S)[1] + 1)
+    held = []
+    for s2k, tk in zip(s2, plain):
+        s = math.sqrt(s2k)
+        while tk > 0 and math.isfinite(s) and math.ldexp(s, tk) >= ceiling:
+            tk -= 1
+        held.append(tk)
+    return t, plain, held
+
+
+# ---------------------------------------------------------------------------------------- the tests
 
 
 def _hex32(a):
@@ -143,3 +166,43 @@ def test_algebra_transforms_geometry_index_and_cap_plain_and_under_sanitizers(ru
             assert dflt == shifts(list(s2), list(mx), 4096.0)  # the default headroom is today's
             assert tight == shifts(list(s2), list(mx), 163.75) and all(a <= b for a, b in zip(tight, dflt))
     assert any(a < b for (s2, mx) in cal[2:] for a, b in zip(shifts(list(s2), list(mx), 163.75), shifts(list(s2), list(mx), 4096.0)))  # the tighter guard bites somewhere
+
+
+def _sq(v):
+    return [x * x for x in v]
+
+
+SMALL = 1.5 * 2.0**-8
+# (what, s2, global shift, the unguarded t_k, t_k under the ceiling 2): the named cases, with what the rule must give written out
+GUARD_NAMED = [
+    ("M8's shape: a median at 2^-8 beside a unit channel and one in [0.75, 1)", _sq([SMALL, SMALL, SMALL, 1.0, 0.75]), 8, [8] * 5, [8, 8, 8, 0, 1]),
+    ("exactly at the ceiling drops, just under it stays", _sq([SMALL] * 5 + [2.0**-7, float(np.nextafter(2.0**-7, 0.0))]), 8, [8] * 7, [8] * 5 + [7, 8]),
+    ("a dead channel and an infinite one keep the global shift", _sq([SMALL] * 5) + [math.inf, 0.0, 1.0], 8, [8] * 8, [8] * 7 + [0]),
+    ("nothing to go by", [math.nan], 0, [0], [0]),
+    ("t = 16", _sq([2.0**-30] * 5 + [1.0, 2.0**-16, 2.0**-15]), 16, [16] * 8, [16] * 5 + [0, 16, 15]),
+    ("t = 0: the guard cannot act", _sq([1.0, 4.0, 100.0, 0.75]), 0, [0] * 4, [0] * 4),
+    ("a lifted channel sits in [1, 2), under the ceiling", _sq([1.0, 1.0, 1.0, 0.99 * 2.0**-8, 1.99 * 2.0**-8]), 0, [0, 0, 0, 9, 8], [0, 0, 0, 9, 8]),
+    ("the guard stops at 0", _sq([SMALL] * 3 + [1e30]), 8, [8] * 4, [8, 8, 8, 0]),
+]
+
+
+def test_the_estimates_ceiling_agrees_with_its_restatement_plain_and_under_sanitizers(rule_checks, tmp_path):
+    rng = np.random.default_rng(12)
+    cases = [(s2, CEILING) for _, s2, _, _, _ in GUARD_NAMED]
+    for _ in range(300):
+        n = int(rng.integers(1, 12))
+        s = np.exp2(rng.uniform(-20, 4, n)) * (rng.random(n) > 0.1)  # one channel in ten dead
+        cases.append((list(s * s), CEILING if rng.random() < 0.7 else float(np.exp2(rng.integers(-2, 9)))))
+    text = "".join("C %s %d %s\n" % (_hex64([c]), len(s2), _hex64(s2)) for s2, c in cases)
+    (tmp_path / "cases.txt").write_text(text)
+    for what, s2, t, plain, held in GUARD_NAMED:
+        assert guarded_shifts(s2, CEILING) == (t, plain, held), what  # the restatement gives what is written out
+    for exe in rule_checks:
+        rows = _run(exe, tmp_path / "cases.txt")
+        assert len(rows) == len(cases)
+        acted = 0
+        for (s2, c), row in zip(cases, rows):
+            t, plain, held = ([int(x) for x in part.split()] for part in row.split("|"))
+            assert (t[0], plain, held) == guarded_shifts(s2, c), (s2, c, row)
+            acted += sum(a < b for a, b in zip(held, plain))
+        assert acted > 100  # the sweep does meet the guard

@@ -7,6 +7,7 @@
 //   O <36 x u32>            a 6x6 M (f32)                 -> the 16 values of Y = A^T M A (winof4_output_2d<float>)
 //   D <9 x u64> <36 x u64>  a 3x3 g and a 6x6 d (f64)     -> the 16 values of A^T [(G g G^T) . (B^T d B)] A in float64
 //   S <h x u64> <n> <n x u64 s2> <n x u64 abs_max>        -> calibrated_stream_shifts with the DEFAULT headroom, then with headroom h
+//   C <c x u64> <n> <n x u64 s2>                          -> the global shift | stream_shifts with the DEFAULT (no) ceiling | with ceiling c
 // Everything that needs no outside opinion -- geometry, the U index, winof4_u's decoding, the cap -- is checked in here.
 #include <cinttypes>
 #include <cstdio>
@@ -77,6 +78,7 @@ static void check_cap() {
         for (float x : row) m = std::max(m, fabsf(x));
     CHECK(m == 65500.0f && std::isfinite((float)(_Float16)m), "worst-case |V| = %g", m);
     CHECK(WINOF4_CAL_HEADROOM == 163.75 && STREAM_CAL_HEADROOM == 4096.0, "calibration headrooms");
+    CHECK(WINOF4_STREAM_CEILING == 2.0 && std::isinf(STREAM_NO_CEILING) && STREAM_NO_CEILING > 0, "the estimate's ceiling");
 }
 
 // the U index: a bijection from (f, co, ci, part) onto [0, 36 x cout_pad x cin_pad x 2)
@@ -209,6 +211,26 @@ int main(int argc, char** argv) {
             for (int t : calibrated_stream_shifts(s2, mx)) printf("%d ", t);
             printf("| ");
             for (int t : calibrated_stream_shifts(s2, mx, headroom)) printf("%d ", t);
+            printf("\n");
+        } else if (kind == 'C') {
+            uint64_t w = 0;
+            size_t n = 0;
+            ss >> w;
+            const double ceiling = f64_of(w);
+            ss >> std::dec >> n >> std::hex;
+            std::vector<double> s2(n);
+            for (double& x : s2) ss >> w, x = f64_of(w);
+            const std::vector<int> plain = stream_shifts(s2), none = stream_shifts(s2, STREAM_NO_CEILING), held = stream_shifts(s2, ceiling);
+            CHECK(plain == none, "the default is no ceiling");
+            const int t = stream_shift_global(s2);
+            for (size_t k = 0; k < n; k++) {
+                CHECK(plain[k] == stream_shift_channel(s2[k], t), "channel %zu: the unguarded rule moved", k);
+                CHECK(held[k] >= 0 && held[k] <= plain[k], "channel %zu: guarded %d, unguarded %d", k, held[k], plain[k]);
+            }
+            printf("%d | ", t);
+            for (int x : plain) printf("%d ", x);
+            printf("| ");
+            for (int x : held) printf("%d ", x);
             printf("\n");
         } else {
             CHECK(false, "unknown case '%c'", kind);
