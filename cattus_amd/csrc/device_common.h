@@ -149,6 +149,83 @@ __device__ __forceinline__ void sp_tap_rows(int (&rowa)[9][NPB], int board_row, 
     }
 }
 
+// ---- split-precision tower: the epilogue its per-layer kernels share (K1s, K1s', K1sk) ----
+// the 8 couts 8 cg .. 8 cg + 7 of staged pixel row px (kernels.hip, stage_tile: f32 [px][32 CB couts], 16-byte slots XORed with px & 7)
+__device__ __forceinline__ void staged_read(float (&v)[8], const char* rowp, int px, int cg) {
+    const f32x4 lo = *reinterpret_cast<const f32x4*>(rowp + (((2 * cg) ^ (px & 7)) << 4));
+    const f32x4 hi = *reinterpret_cast<const f32x4*>(rowp + (((2 * cg + 1) ^ (px & 7)) << 4));
+#pragma unroll
+    for (int j = 0; j < 4; j++) v[j] = lo[j], v[4 + j] = hi[j];
+}
+
+// Rows of `in` / `res` / `out`: 4 bytes per channel, the hi values of cout c at element sp_col(c), the lo values 32 further.
+__device__ __forceinline__ int sp_col(int c) { return (c >> 5) * 64 + (c & 31); }
+
+// One pixel row's 8 accumulator sums to its stores: the lane's 8 couts from `col` on of tower row `row`.  Times the inverse weight
+// scale plus bias (the accumulator carries the weights' power-of-two scale, so the product is exact and the fused multiply-add
+// rounds as a multiply followed by an add would), + skip as hi + lo (exact in f32: lo is at most half an ulp of hi, 22 significant
+// bits), ReLU, then either plain f32 rows (flags & CONV_OUT_F32: the tower's last layer, for the head kernels or a Winograd
+// tower's stem) or the clamp at 65504 and the split into (hi, lo).  Pixel slots past the board (!valid) stay zero: masked once,
+// on the packed vectors.  Stores: non-temporal on the full grid (CB = 2), where a layer's 16.7 MB of output and its 2.4 MB of
+// weights do not fit the XCDs' L2 together; plain on the small-grid tile (CB = 1, <= 128 leaves of an 8x8 game), where the output
+// stays in the L2 of the XCD whose workgroups read it back as the next layer's input (xcd_remap keeps a row block on one XCD):
+// 18.5 us per launch against 19.9 with non-temporal stores at batch 64, no difference at 128.
+template <int CB, bool HAS_RES>
+__device__ __forceinline__ void finish_f16x2_sums(float (&v)[8], const f32x4 (&ds8)[2], const f32x4 (&bias8)[2], const _Float16 (&resv)[16], bool valid,
+                                                  int flags, unsigned* sat, _Float16* out, size_t row, int cout, int col) {
+    typedef _Float16 T;
+#pragma unroll
+    for (int j = 0; j < 8; j++) v[j] = __builtin_fmaf(v[j], ds8[j >> 2][j & 3], bias8[j >> 2][j & 3]);
+    if (HAS_RES) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) v[j] = v[j] + ((float)resv[j] + (float)resv[8 + j]);
+    }
+    float y[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) y[j] = v[j] > 0.0f ? v[j] : 0.0f;
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    if (flags & CONV_OUT_F32) {
+        if (flags & CONV_WINO_IN) cap_wino_input(y, valid, sat);
+        else if (flags & CONV_WINOF4_IN) cap_winof4_input(y, valid, sat);
+        float* of = reinterpret_cast<float*>(out) + row * (size_t)cout + col;
+        const f32x4 y0 = valid ? *reinterpret_cast<f32x4*>(y) : zero4, y1 = valid ? *reinterpret_cast<f32x4*>(y + 4) : zero4;
+        if constexpr (CB == 2) {
+            __builtin_nontemporal_store(y0, reinterpret_cast<f32x4*>(of));
+            __builtin_nontemporal_store(y1, reinterpret_cast<f32x4*>(of) + 1);
+        } else {
+            reinterpret_cast<f32x4*>(of)[0] = y0;
+            reinterpret_cast<f32x4*>(of)[1] = y1;
+        }
+    } else {
+        const size_t off = row * ((size_t)cout * 2) + sp_col(col);
+        T hi[8], lo[8];
+        note_saturation(y, valid, sat);
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const float yc = y[j] < 65504.0f ? y[j] : 65504.0f;  // saturate instead of overflowing to infinity
+            hi[j] = (T)yc;
+            lo[j] = (T)(yc - (float)hi[j]);
+        }
+        const f32x4 hi4o = valid ? *reinterpret_cast<f32x4*>(hi) : zero4, lo4o = valid ? *reinterpret_cast<f32x4*>(lo) : zero4;
+        if constexpr (CB == 2) {
+            __builtin_nontemporal_store(hi4o, reinterpret_cast<f32x4*>(out + off));
+            __builtin_nontemporal_store(lo4o, reinterpret_cast<f32x4*>(out + off + 32));
+        } else {
+            *reinterpret_cast<f32x4*>(out + off) = hi4o;
+            *reinterpret_cast<f32x4*>(out + off + 32) = lo4o;
+        }
+    }
+}
+// The same from a staged pixel row (stage_tile): K1s and K1s'.
+template <int CB, bool HAS_RES>
+__device__ __forceinline__ void finish_f16x2(const char* rowp, int px, int cg, const f32x4 (&ds8)[2], const f32x4 (&bias8)[2],
+                                             const _Float16 (&resv)[16], bool valid, int flags, unsigned* sat, _Float16* out, size_t row,
+                                             int cout, int col) {
+    float v[8];
+    staged_read(v, rowp, px, cg);
+    finish_f16x2_sums<CB, HAS_RES>(v, ds8, bias8, resv, valid, flags, sat, out, row, cout, col);
+}
+
 // ---- host side: a kernel family's instances, listed once ----
 // Next to its kernels every templated family has one for_each_* visitor.  It calls f(kernel, ..., template arguments as
 // std::integral_constant values) for every instance that exists; an `if constexpr` on the family's rule keeps the other

@@ -335,6 +335,10 @@ enum class TowerKind {
     // the same tower with every layer behind the stem in Winograd F(4x4, 3x3) form (kernels_winof4.hip): only for tower_form WINOGRAD_F4,
     // never by AUTO; other bits than the F(2x2) kinds, activations capped at WINOF4_ACT_MAX, always one launch per layer
     WinoF4,
+    // f16x2, 64-slot boards, 128 .. SK_MAX_FILTERS filters: the per-layer direct tower with the K walk of every layer behind the stem divided
+    // over the waves of a workgroup (kernels_splitk.hip), for batches of a few leaves: only for tower_form DIRECT_SPLITK, never by AUTO; its
+    // f32 summation order, and so its bits, are its own; rows in the direct form's layout
+    DirectSplitK,
 };
 struct TowerPlan {
     TowerKind kind = TowerKind::Generic;
@@ -373,6 +377,7 @@ struct cattus_eval {
     // leaves runs the layers behind the stem on the small-tile kernel (kernels_wino4s.hip), the same bits; tail_batches counts those passes
     uint32_t tail_leaves = 0;
     std::atomic<uint64_t> tail_batches{0};
+    int splitk_forced = 0;  // CATTUS_SPLITK_WAYS=1|2|4|8: the way count of the split-K direct form (tests and A/B; 0: splitk_rule.h's rule)
     // the f16 towers carry the residual stream at 2^stream_shift times its size, channel k of it at 2^stream_shifts[k] >= that
     // (choose_stream_shift; from cattus_hip_create_calibrated: calibrated_stream_shifts, whose headroom guard can take a channel
     // below the global shift, as the F(4x4) tower's ceiling on the estimate can); CATTUS_STREAM_SHIFT=0: never
@@ -844,6 +849,12 @@ struct Forward {
 
     // Layer l of the per-layer tower -- 0: the stem; 2i + 1: block i's conv1, a -> t; 2i + 2: its conv2 + skip, t -> y, which becomes a --
     // in layer order; returns the buffer it wrote.  (cattus_hip_trace steps the shadow's pass through this, one layer per point.)
+    // One layer behind the stem of the split-K direct tower: conv_mfma's arguments, the split-K launcher
+    void conv_splitk(const ConvLayer& c, const void* in, const void* res, void* out, int flags) {
+        hipEvent_t s0 = ev(), s1 = ev();
+        launch_conv3x3_splitk(in, c.w.p, c.b.as<float>(), res, out, nb, FP, FP, S, st, s0, s1, flags, e->splitk_forced, e->conv_opts.saturated);
+    }
+
     const void* per_layer_step(uint32_t l) {
         const int last_flags = act_f16_family(e->act) && l == 2 * d.blocks ? CONV_OUT_F32 : 0;  // the f16 towers hand the f32 head kernels plain f32 rows
         if (l == 0) {
@@ -851,11 +862,14 @@ struct Forward {
             return a;
         }
         const uint32_t i = (l - 1) / 2;
+        const bool sk = e->plan.kind == TowerKind::DirectSplitK;
         if (l & 1) {
-            conv_mfma(*e->c1[i], a, nullptr, t, 0);
+            if (sk) conv_splitk(*e->c1[i], a, nullptr, t, 0);
+            else conv_mfma(*e->c1[i], a, nullptr, t, 0);
             return t;
         }
-        conv_mfma(*e->c2[i], t, a, y, last_flags);
+        if (sk) conv_splitk(*e->c2[i], t, a, y, last_flags);
+        else conv_mfma(*e->c2[i], t, a, y, last_flags);
         std::swap(a, y);
         return a;
     }
@@ -941,6 +955,7 @@ int enqueue_forward(cattus_eval* e, Lane& L, const uint64_t* d_planes, uint32_t 
         case TowerKind::Simple: f.simple(); break;
         case TowerKind::Generic: f.heads_generic(f.generic()); break;
         case TowerKind::PerLayer: f.heads_mfma(f.per_layer()); break;
+        case TowerKind::DirectSplitK: f.heads_mfma(f.per_layer()); break;  // the stem through conv_mfma, every layer behind it through conv_splitk
         case TowerKind::Resident64: f.resident64(), f.heads_mfma(nullptr); break;
         case TowerKind::Resident64Split: f.heads_mfma(f.resident64_split()); break;
         case TowerKind::Wino16:
@@ -1264,6 +1279,7 @@ CATTUS_API const char* cattus_hip_tower_kernel(const cattus_eval* e) {
         case TowerKind::Wino16: return "conv3x3_wino_kernel";
         case TowerKind::Wino4: return one_launch_now(e, e->bpad) ? "tower_wino4_kernel" : "conv3x3_wino4_kernel";
         case TowerKind::WinoF4: return "conv3x3_winof4_kernel";
+        case TowerKind::DirectSplitK: return "conv3x3_splitk_kernel";
         case TowerKind::PerLayer: break;
     }
     return e->act != Act::F16S ? "conv3x3_mfma_v2_kernel" : e->plan.w_frag ? "conv3x3_splitw_kernel" : "conv3x3_split_kernel";
@@ -1272,6 +1288,15 @@ CATTUS_API const char* cattus_hip_tower_kernel(const cattus_eval* e) {
 CATTUS_API int cattus_hip_tail_leaves(const cattus_eval* e, uint32_t* effective) {
     if (!e || !effective) return fail(CATTUS_E_INVALID, "NULL argument");
     *effective = e->tail_leaves;
+    return CATTUS_OK;
+}
+
+CATTUS_API int cattus_hip_splitk_plan(const cattus_eval* e, uint32_t* ways, uint32_t* bounds) {
+    if (!e || !ways) return fail(CATTUS_E_INVALID, "NULL argument");
+    if (e->plan.kind != TowerKind::DirectSplitK) return fail(CATTUS_E_UNSUPPORTED, "splitk_plan: the evaluator does not run tower_form DIRECT_SPLITK");
+    const int chunks = (int)e->fpad / 32, w = splitk_ways(chunks, e->splitk_forced);
+    *ways = (uint32_t)w;
+    for (int i = 0; bounds && i <= w; i++) bounds[i] = (uint32_t)splitk_bound(chunks, w, i);
     return CATTUS_OK;
 }
 
@@ -1294,7 +1319,7 @@ CATTUS_API int cattus_hip_stem_input(const cattus_eval* e, uint32_t* channels, u
     if (!e) return fail(CATTUS_E_INVALID, "NULL argument");
     if (channels) *channels = e->cpad0;
     // the towers that go through Forward::conv_mfma; the resident ones expand the planes in their one launch
-    if (packed) *packed = (e->plan.kind == TowerKind::PerLayer || e->plan.wino()) && !stem_is_fused(e->d.planes, e->pack_separately);
+    if (packed) *packed = (e->plan.kind == TowerKind::PerLayer || e->plan.kind == TowerKind::DirectSplitK || e->plan.wino()) && !stem_is_fused(e->d.planes, e->pack_separately);
     return CATTUS_OK;
 }
 
@@ -1308,7 +1333,7 @@ struct Switches {
         if (!text) return CATTUS_OK;
         static const char* const known[] = {"CATTUS_CONV_CB", "CATTUS_CONV_PBW", "CATTUS_FUSED_STEM", "CATTUS_T64_CH", "CATTUS_T64_LS", "CATTUS_SPLIT_W",
                                             "CATTUS_T64S_HEADS", "CATTUS_T64S_SHAPE", "CATTUS_TOWER64", "CATTUS_FORCE_GENERIC", "CATTUS_WINO_INPLACE",
-                                            "CATTUS_ARENA", "CATTUS_WINO_KERNEL", "CATTUS_WINO_PERSIST", "CATTUS_WINO_SPIN", "CATTUS_STREAM_SHIFT"};
+                                            "CATTUS_ARENA", "CATTUS_WINO_KERNEL", "CATTUS_WINO_PERSIST", "CATTUS_WINO_SPIN", "CATTUS_STREAM_SHIFT", "CATTUS_SPLITK_WAYS"};
         const std::string s(text);
         size_t at = 0;
         while (at < s.size()) {
@@ -1360,6 +1385,16 @@ int resolve_plan(const cattus_net_desc& d, const cattus_eval_config& cfg, const 
         return fail(CATTUS_E_UNSUPPORTED, "tower_form WINOGRAD_F4 needs dtype f16x2, an 8x8 board, at least one residual block and a multiple of 64 filters (at least 128)");
     TowerPlan& p = *plan = TowerPlan();
     p.w_frag = tuned && act == Act::F16S && !sw.starts("CATTUS_SPLIT_W", '0');
+    // DIRECT_SPLITK: the split-K direct form, only when asked for, whatever max_batch is
+    if (cfg.tower_form == CATTUS_TOWER_DIRECT_SPLITK) {
+        const char* const needs = "tower_form DIRECT_SPLITK needs dtype f16x2 with fragment-order weights, a board of edge <= 8, at least one residual block and a multiple of 64 filters, 128 to 512";
+        if (!(tuned && act == Act::F16S && p.w_frag && d.blocks > 0 && tower_slots(d.board) == 64 && splitk_supported(fpad, fpad, d.board)))
+            return fail(CATTUS_E_UNSUPPORTED, "%s", needs);
+        if (const char* wv = sw.get("CATTUS_SPLITK_WAYS"))
+            if (strcmp(wv, "1") != 0 && strcmp(wv, "2") != 0 && strcmp(wv, "4") != 0 && strcmp(wv, "8") != 0) return fail(CATTUS_E_INVALID, "CATTUS_SPLITK_WAYS is 1, 2, 4 or 8");
+        p.kind = TowerKind::DirectSplitK;
+        return CATTUS_OK;
+    }
     const bool resident = tuned && fpad == 64 && !sw.starts("CATTUS_TOWER64", '0');
     if (!tuned) p.kind = simple ? TowerKind::Simple : TowerKind::Generic;
     else if (cfg.tower_form == CATTUS_TOWER_WINOGRAD_F4) {
@@ -1391,7 +1426,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
     memcpy(&cfg_copy, cfg_in, cfg_in->struct_size);
     cfg_copy.struct_size = sizeof(cattus_eval_config);
     const cattus_eval_config* cfg = &cfg_copy;
-    if (cfg->tower_form > CATTUS_TOWER_WINOGRAD_F4) return fail(CATTUS_E_INVALID, "unknown tower_form %u", cfg->tower_form);
+    if (cfg->tower_form > CATTUS_TOWER_DIRECT_SPLITK) return fail(CATTUS_E_INVALID, "unknown tower_form %u", cfg->tower_form);
     if (cfg->tail_leaves > cfg->max_batch) return fail(CATTUS_E_INVALID, "tail_leaves %u is more than max_batch %u", cfg->tail_leaves, cfg->max_batch);
     Switches sw;
     if (int src = sw.parse(switches)) return src;
@@ -1457,6 +1492,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
     e->t64s_depth = sw.number("CATTUS_T64S_SHAPE");
     e->conv_opts.cb = sw.number("CATTUS_CONV_CB");
     e->conv_opts.pbw = sw.number("CATTUS_CONV_PBW");
+    e->splitk_forced = sw.number("CATTUS_SPLITK_WAYS");
     e->hw = d.board * d.board;
     e->act = simple ? Act::F32
              : cfg->dtype == CATTUS_DTYPE_BF16 ? Act::BF16

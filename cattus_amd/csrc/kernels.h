@@ -9,6 +9,7 @@
 #include "legal_span.h"   // the ragged layout of the leaf server's legal-move lists
 #include "tap_layout.h"   // TapSource, TraceRecord: where a point's activations live, the rule of a trace record
 #include "winof4_rule.h"  // the Winograd F(4x4, 3x3) form: matrices, transforms, geometry, cap, U index
+#include "splitk_rule.h"  // the split-K direct form: ways, ranges, reduction order, grid map, LDS plan
 
 namespace cattus {
 
@@ -126,6 +127,17 @@ void launch_tower_wino4(const Wino4TowerLayer* d_layers, uint32_t nlayers, unsig
 void launch_conv3x3_wino4s(const float* in, const void* wu, const float* bias, const float* res, float* out, uint32_t bpad, uint32_t cin,
                            uint32_t cout, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, unsigned* sat);
 hipError_t prepare_wino4s();
+
+// ---- K1sk: the direct split-precision layer with the K walk divided over the waves of a workgroup (kernels_splitk.hip; splitk_rule.h has the
+// split, the reduction order, the grid map and the LDS plan) ----
+// The arguments of launch_conv3x3_mfma's Act::F16S layer with CONV_W_FRAG: in / res / out rows of (hi, lo) pairs on 64-slot boards (S <= 8), wf
+// the fragment-ordered weights, bias = [cout biases | cout inverse scales]; flags & CONV_OUT_F32 as there.  Workgroup = one board x 32 couts,
+// grid boards x (cout / 32), W = splitk_ways(cin / 32, forced_ways) waves; its bits are those of the direct kernels only for W = 1.
+// splitk_supported: cin and cout multiples of 64, 128 .. SK_MAX_FILTERS; anything else aborts.
+bool splitk_supported(uint32_t cin, uint32_t cout, uint32_t S);
+void launch_conv3x3_splitk(const void* in, const void* wf, const float* bias, const void* res, void* out, uint32_t boards, uint32_t cin, uint32_t cout,
+                           uint32_t S, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, int flags, int forced_ways, unsigned* sat);
+hipError_t prepare_splitk();  // its dynamic-LDS opt-in; called by prepare_device()
 
 // ---- K1f4: the split-precision conv in Winograd F(4x4, 3x3) form (kernels_winof4.hip; winof4_rule.h has the rule) ----
 // The arguments of launch_conv3x3_wino4: in / res / out plain f32 rows on 64-slot boards, res may be out; wu = G g G^T as (hi, lo) f16

@@ -73,6 +73,7 @@ ABI_SYMBOLS = [
     "cattus_hip_stream_shift",  # include/cattus_hip_diag.h
     "cattus_hip_stream_shifts",  # include/cattus_hip_diag.h
     "cattus_hip_stem_input",  # include/cattus_hip_diag.h
+    "cattus_hip_splitk_plan",  # include/cattus_hip_diag.h
 ]
 
 
@@ -95,13 +96,13 @@ class EvalConfig(C.Structure):
     ]
 
 
-TOWER_FORMS = {"auto": 0, "direct": 1, "winograd": 2, "winograd_f4": 3}  # cattus_tower_form
+TOWER_FORMS = {"auto": 0, "direct": 1, "winograd": 2, "winograd_f4": 3, "direct_splitk": 4}  # cattus_tower_form
 # Diagnostic switches (include/cattus_hip_diag.h).  The library reads none of them from the environment; this binding -- the
 # harness of the tests and the timing scripts -- forwards the ones it finds there through cattus_hip_create_diag, so that
 # `CATTUS_TOWER64=0 python scripts/...` and monkeypatch.setenv keep working.  CATTUS_WINOGRAD=0/1 (rounds 3-4) maps to tower_form.
 DIAG_SWITCHES = ("CATTUS_CONV_CB", "CATTUS_CONV_PBW", "CATTUS_FUSED_STEM", "CATTUS_T64_CH", "CATTUS_T64_LS", "CATTUS_SPLIT_W", "CATTUS_T64S_HEADS",
                  "CATTUS_T64S_SHAPE", "CATTUS_TOWER64", "CATTUS_FORCE_GENERIC", "CATTUS_WINO_INPLACE", "CATTUS_ARENA", "CATTUS_WINO_KERNEL",
-                 "CATTUS_WINO_PERSIST", "CATTUS_WINO_SPIN", "CATTUS_STREAM_SHIFT")
+                 "CATTUS_WINO_PERSIST", "CATTUS_WINO_SPIN", "CATTUS_STREAM_SHIFT", "CATTUS_SPLITK_WAYS")
 
 
 class Stats(C.Structure):
@@ -232,6 +233,7 @@ def load_library():
     L.cattus_hip_stream_shift.argtypes = [vp]
     L.cattus_hip_stream_shifts.argtypes = [vp, C.POINTER(C.c_int), C.c_uint32]
     L.cattus_hip_stem_input.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.cattus_hip_splitk_plan.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.cattus_hip_verify.argtypes = [vp, vp, C.c_size_t, C.c_uint32]
     L.cattus_hip_verify_stats.argtypes = [vp, C.POINTER(VerifyStats)]
     L.cattus_hip_verify_worst_planes.argtypes = [vp, u64p]
@@ -326,8 +328,9 @@ class HipEvaluator:
         verify_every: int = 0,
         tail_leaves: int = 0,
     ):
-        """tower_form: "auto" | "direct" | "winograd" | "winograd_f4" (cattus_tower_form; None = "auto", or what CATTUS_WINOGRAD=0/1 in the
-        environment says; "winograd_f4", the F(4x4,3x3) form, is opt-in only: never what "auto" picks).  switches: diagnostic switches for cattus_hip_create_diag (None = the CATTUS_* ones found in the
+        """tower_form: "auto" | "direct" | "winograd" | "winograd_f4" | "direct_splitk" (cattus_tower_form; None = "auto", or what CATTUS_WINOGRAD=0/1 in the
+        environment says; "winograd_f4", the F(4x4,3x3) form, and "direct_splitk", the direct form with the K walk divided over a workgroup's waves
+        for batches of a few leaves, are opt-in only: never what "auto" picks, and each has bits of its own).  switches: diagnostic switches for cattus_hip_create_diag (None = the CATTUS_* ones found in the
         environment, {} = none).  calibration: sample positions, uint64 ``[n, C, plane_words]`` -- the f16 / f16x2 towers then
         take their stream shifts from the range measured on them instead of from the BatchNorm parameters
         (cattus_hip_create_calibrated; nothing to calibrate for f32 / bf16, which come out as without it).  verify_every: N >= 1
@@ -637,6 +640,15 @@ class HipEvaluator:
         t = C.c_double()
         _check(self._lib.cattus_hip_mfma_sustained(self._h, float(seconds), C.byref(t)))
         return t.value
+
+    def splitk_plan(self) -> tuple[int, list[int]]:
+        """(W, boundaries) of a tower_form="direct_splitk" evaluator: wave w of a workgroup walks the 32-channel input chunks
+        boundaries[w] .. boundaries[w + 1] - 1 of every layer behind the stem (include/cattus_hip_diag.h).  A function of the filter count
+        alone (and of CATTUS_SPLITK_WAYS); any other evaluator raises CattusHipError with status -2."""
+        ways = C.c_uint32()
+        bounds = (C.c_uint32 * 9)()
+        _check(self._lib.cattus_hip_splitk_plan(self._h, C.byref(ways), bounds))
+        return ways.value, [int(b) for b in bounds[: ways.value + 1]]
 
     def tail_leaves(self) -> int:
         """``tail_leaves`` as it holds for this evaluator: what it was created with on a Winograd F(2x2,3x3) plan, 0 on every other."""

@@ -597,6 +597,16 @@ def write_summary(path, summary: dict):
         json.dump(out, f)
 
 
+def tower_form_from_inference(inf: dict) -> str:
+    """model.inference.tower_form of the engine JSON: one of the evaluator's TOWER_FORMS names, "auto" when absent."""
+    from .evaluator import TOWER_FORMS
+
+    form = inf.get("tower_form", "auto")
+    if form not in TOWER_FORMS:
+        raise SystemExit(f"model.inference.tower_form is one of {sorted(TOWER_FORMS)}, got {form!r}")
+    return form
+
+
 def main(argv=None):
     import argparse
 
@@ -627,11 +637,15 @@ def main(argv=None):
     # optional: batches of at most this many leaves on the Winograd tower's small-tile kernel (cattus_eval_config.tail_leaves: the same bits);
     # absent or 0: off
     tail_leaves = int(inf.get("tail_leaves", 0))
+    # optional: the form of the f16x2 tower (cattus_tower_form): "auto" (absent), "direct", "winograd", "winograd_f4", or "direct_splitk" -- the
+    # direct form for batches of a few leaves, the reference's threads: 8, batch_size: 1 (include/cattus_hip.h)
+    tower_form = tower_form_from_inference(inf)
 
     def load(path):
         blob = Path(path).read_bytes()
         return HipEvaluator(blob, batch_size=engine["model"]["batch_size"], plane_words=info["plane_words"],
-                            dtype=inf.get("dtype", "f16x2"), device=inf.get("device", 0), verify_every=verify_every, tail_leaves=tail_leaves)
+                            dtype=inf.get("dtype", "f16x2"), device=inf.get("device", 0), verify_every=verify_every, tail_leaves=tail_leaves,
+                            tower_form=tower_form)
 
     ev1 = load(args.model1_path)
     same = os.path.abspath(args.model1_path) == os.path.abspath(args.model2_path)

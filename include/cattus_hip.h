@@ -68,6 +68,31 @@ typedef enum cattus_tower_form {
      * Range: activations are capped at 655 in stream units -- 25x tighter than the other Winograd form's 16376 -- and a stream is
      * never shifted DOWN: a network whose activations pass 655 counts in cattus_stats.saturated and belongs on another form. */
     CATTUS_TOWER_WINOGRAD_F4 = 3,
+    /* Direct 3x3 with the K walk of every layer behind the stem divided over the waves of a workgroup (conv3x3_splitk_kernel), for
+     * evaluators whose batches hold a few leaves: the reference's threading model (threads: 8, batch_size: 1) through the leaf server.
+     * A workgroup takes one board x 32 output channels; its W waves (8 from 256 filters on, 4 below: a function of the filter count
+     * alone) each walk a contiguous range of 32-channel input chunks and the W partial sums are added in f32 as a pairwise tree by
+     * wave index.  Opt-in: NEVER chosen by AUTO, legal for any max_batch.  Coverage: f16x2, a board of edge <= 8, at least one residual
+     * block, a multiple of 64 filters from 128 to 512, else CATTUS_E_UNSUPPORTED.  ITS BITS ARE ITS OWN -- another f32 summation order
+     * than DIRECT's, of the same quality (tests/test_splitk_gpu.py holds its error against float64 to at most twice DIRECT's) -- and a
+     * leaf's bits still do not depend on its batch.  tail_leaves is ignored.  cattus_hip_splitk_plan() (cattus_hip_diag.h) reports W and
+     * the waves' ranges.
+     * MEASURED on one MI355X (scripts/splitk_time.py -> profiles/splitk_latency.txt: one process, max_batch = n, the forms alternating, 5 windows
+     * of 200 steps through cattus_hip_eval_device, median; DIRECT | DIRECT_SPLITK, ms per step (us per conv launch)), chess 20x256:
+     *   1 leaf 0.522 (11.7) | 0.398 (8.6),  4: 0.523 (11.7) | 0.399 (8.6),  8: 0.526 (11.7) | 0.407 (8.9),  16: 0.528 (11.8) | 0.414 (9.0),
+     *   32: 0.532 (11.8) | 0.461 (10.1),  64: 0.589 (13.3) | 0.800 (18.5),  128: 0.978 (23.0) | 1.472 (35.1);
+     * chess 4x128:  0.083 (7.7) | 0.076 (6.1) at 1 leaf ... 0.089 (8.6) | 0.084 (8.3) at 64,  0.093 (7.7) | 0.107 (9.3) at 128.
+     * (A second run on another box is in the same file; ranges below are over both.)
+     * Against the 12 % by which two boxes differ on one binary: RECOMMENDED UP TO 16 LEAVES PER BATCH ON 256 FILTERS (21-24 % faster per
+     * step); at 32 leaves it is 8-13 % faster, which that spread covers; FROM 64 LEAVES ON IT IS 1.4-1.5x SLOWER (one workgroup per board and 32
+     * couts, each fetching the whole 288 KiB of its cout block's weights).  On 128 filters the 5-9 % it gains up to 64 leaves are inside
+     * the spread: not recommended there, and slower at 128.  The estimate it was built on -- the K loop's half of a launch falling 4-8x --
+     * WAS MISSED: a launch falls from 11.7 to 8.6 us, not to ~7.  Forced way counts (1 | 2 | 4 | 8 ways: 23.7 | 13.9 | 9.8 | 8.6 us): each
+     * doubling saves half of what the one before did, and 4 -> 8 ways only 1.2 us: what binds is the ~7.4 us that no split divides --
+     * dispatch, the first loads (a wave's image and its chunk's 36 KiB of weights), the exchange and the epilogue.  16 blocking threads with one leaf per call through the leaf server
+     * (9-12 leaves per batch, Python threads around cattus_hip_apply): 17.3-19.2 k -> 21.1-27.0 k leaves/s on chess 20x256.  Not measured:
+     * in-kernel stamps or counters of the new kernel, filter counts other than 128 and 256, two evaluators sharing a device. */
+    CATTUS_TOWER_DIRECT_SPLITK = 4,
 } cattus_tower_form;
 
 /* Replaces the reference's InferenceConfig + batch_size (engine/src/net/model.rs:17-25,

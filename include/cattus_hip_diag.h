@@ -29,6 +29,9 @@ extern "C" {
  *                           polls a hand-off wait of that launch may take before it gives up (a launch that gave up is run again,
  *                           per layer: the tests set 1 to walk that path)
  *   CATTUS_WINO_INPLACE=0, CATTUS_ARENA=0     memory plan of the Winograd tower (a third activation buffer; separate allocations)
+ *   CATTUS_SPLITK_WAYS=1|2|4|8   tower_form DIRECT_SPLITK: the number of waves a layer's K walk is divided over, instead of the rule's (8 from
+ *                           256 filters on, 4 below; never more than there are 32-channel chunks).  THIS ONE CHANGES THE SUMMATION ORDER and with
+ *                           it the bits (tests and A/B timing only); 1 gives tower_form DIRECT's bits
  * One switch does change what a leaf evaluates to, and exists to show why its default is what it is:
  *   CATTUS_STREAM_SHIFT=0   the f16 / f16x2 towers carry the residual stream at its own size, however small (see below) */
 int cattus_hip_create_diag(const void* weights, size_t nbytes, const cattus_eval_config* cfg, const char* switches, cattus_eval** out);
@@ -58,6 +61,12 @@ int cattus_hip_stream_shifts(const cattus_eval* e, int* out, uint32_t n);
  * plane pack runs as its own launch in front of the stem (per-layer and Winograd towers of a network of more than 32 planes, or under
  * CATTUS_FUSED_STEM=0), 0 where the stem kernel or a one-launch tower expands the planes itself.  Either pointer may be NULL. */
 int cattus_hip_stem_input(const cattus_eval* e, uint32_t* channels, uint32_t* packed);
+
+/* The K split of a tower_form DIRECT_SPLITK evaluator (CATTUS_E_UNSUPPORTED on every other): *ways = W, the waves of a workgroup, and, where
+ * bounds is not NULL, bounds[0 .. W] = the boundaries of their ranges of 32-channel input chunks -- wave w walks chunks bounds[w] .. bounds[w + 1]
+ * - 1 of every layer behind the stem, bounds[0] = 0, bounds[W] = padded filters / 32.  bounds needs room for W + 1 entries; W <= 8, so 9 always
+ * suffice.  A function of the filter count (and of CATTUS_SPLITK_WAYS): the same for every max_batch. */
+int cattus_hip_splitk_plan(const cattus_eval* e, uint32_t* ways, uint32_t* bounds);
 
 /* The comparison kernel of cattus_hip_verify (cattus_hip.h) on host arrays, so that tests can feed it what no network produces.
  * policy_a / policy_b: [n][moves], value_a / value_b: [n], b the reference side; records: n x 16 bytes, per leaf

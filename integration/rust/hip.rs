@@ -35,6 +35,8 @@ struct CattusEvalConfig {
     flush_us: u32,
     /// cattus_tower_form: 0 = auto (Winograd form of the f16x2 tower for batch_size >= 192), 1 = direct, 2 = Winograd F(2x2,3x3),
     /// 3 = Winograd F(4x4,3x3) (opt-in, never what auto picks; activations capped at 655: see include/cattus_hip.h)
+    /// 4 = direct with the K walk split over a workgroup's waves (opt-in, never what auto picks; bits of its own): for evaluators whose
+    /// batches hold a few leaves -- threads: 8, batch_size: 1 through the leaf server; slower than direct from 64 leaves on
     tower_form: u32,
     /// batches of at most this many leaves of the Winograd F(2x2,3x3) tower run on its small-tile kernel: the same bits, more workgroups
     /// for a short batch; 0 = off; ignored on every other plan (uint32_t tail_leaves of include/cattus_hip.h)
