@@ -335,6 +335,10 @@ enum class TowerKind {
     // the same tower with every layer behind the stem in Winograd F(4x4, 3x3) form (kernels_winof4.hip): only for tower_form WINOGRAD_F4,
     // never by AUTO; other bits than the F(2x2) kinds, activations capped at WINOF4_ACT_MAX, always one launch per layer
     WinoF4,
+    // dtype f16w (Act::F16 with this kind, and no other kind for that dtype): the stem on the direct f16 kernel, every layer behind it in
+    // Winograd F(2x2, 3x3) form with ONE f16 term per product and f32 rows between the layers (kernels_wino_f16.hip); bits of its own,
+    // activations capped at WINO_ACT_MAX, always one launch per layer
+    WinoF16,
     // f16x2, 64-slot boards, 128 .. SK_MAX_FILTERS filters: the per-layer direct tower with the K walk of every layer behind the stem divided
     // over the waves of a workgroup (kernels_splitk.hip), for batches of a few leaves: only for tower_form DIRECT_SPLITK, never by AUTO; its
     // f32 summation order, and so its bits, are its own; rows in the direct form's layout
@@ -348,7 +352,7 @@ struct TowerPlan {
     // a layer has more tiles than the device has CUs (CATTUS_WINO_PERSIST=0: per-layer launches) -- for the batches one_launch_now() admits
     bool one_launch = false;
     bool tuned() const { return kind != TowerKind::Simple && kind != TowerKind::Generic; }  // the MFMA NHWC towers
-    bool wino() const { return kind == TowerKind::Wino16 || kind == TowerKind::Wino4 || kind == TowerKind::WinoF4; }  // f32 rows between the layers
+    bool wino() const { return kind == TowerKind::Wino16 || kind == TowerKind::Wino4 || kind == TowerKind::WinoF4 || kind == TowerKind::WinoF16; }  // f32 rows between the layers
 };
 
 }  // namespace
@@ -518,6 +522,7 @@ int upload_conv(cattus_eval* e, ConvLayer& L, const Folded& f, uint32_t cout, ui
         std::vector<int> sh;
         const std::vector<double> U = wino_transform(f, s, &sh);
         if ((rc = up(L.b, bias_and_scales(f, s, &sh)))) return rc;
+        if (e->plan.kind == TowerKind::WinoF16) return up(L.w, wino_u_f16(U, s, sh), &e->arena);
         return up(L.w, wino_u(U, s, sh), &e->arena);
     }
     const bool scaled = act_f16_family(e->act);
@@ -575,7 +580,10 @@ int build(cattus_eval* e, const float* p, const Calibration* cal) {
     if (act_f16_family(e->act) && e->stream_shift_on) {
         // (the F(4x4) form's cap is 25x tighter: its headroom is a quarter of that cap, as the default is of the F(2x2) form's)
         const double headroom = plan.kind == TowerKind::WinoF4 ? WINOF4_CAL_HEADROOM : STREAM_CAL_HEADROOM;
-        if (cal) e->stream_shifts = calibrated_stream_shifts(cal->s2, cal->abs_max, headroom), e->stream_shift = stream_shift_global(cal->s2);
+        // (the f16w tower's stream is f32: calibrated, it keeps the estimate's shifts and takes the measured guard alone -- weight_layout.h)
+        if (cal && plan.kind == TowerKind::WinoF16)
+            e->stream_shifts = calibrated_stream_shifts_f32_stream(choose_stream_shift(d, p, &e->stream_shift, STREAM_NO_CEILING), cal->abs_max, headroom);
+        else if (cal) e->stream_shifts = calibrated_stream_shifts(cal->s2, cal->abs_max, headroom), e->stream_shift = stream_shift_global(cal->s2);
         else e->stream_shifts = choose_stream_shift(d, p, &e->stream_shift, plan.kind == TowerKind::WinoF4 ? WINOF4_STREAM_CEILING : STREAM_NO_CEILING);
     }
     const std::vector<int>& tk = e->stream_shifts;
@@ -879,7 +887,7 @@ struct Forward {
         return a;
     }
 
-    // Wino16 / Wino4 / WinoF4: the stem on the direct kernel, every layer behind it in Winograd form, f32 rows between the layers
+    // Wino16 / Wino4 / WinoF4 / WinoF16: the stem on the direct kernel (the split one, or the f16 one under dtype f16w), every layer behind it in Winograd form, f32 rows between the layers
     int wino() {
         const bool f4 = e->plan.kind == TowerKind::WinoF4;
         conv_mfma(e->stem, L.x0.p, nullptr, a, CONV_OUT_F32 | (f4 ? CONV_WINOF4_IN : CONV_WINO_IN), true);
@@ -900,7 +908,7 @@ struct Forward {
             HIP_TRY(hipMemcpyAsync(L.h_tower_err.p, tower_err, 4, hipMemcpyDeviceToHost, st));
             return CATTUS_OK;
         }
-        const auto launch = f4 ? launch_conv3x3_winof4 : tail ? launch_conv3x3_wino4s : e->plan.kind == TowerKind::Wino4 ? launch_conv3x3_wino4 : launch_conv3x3_wino;
+        const auto launch = e->plan.kind == TowerKind::WinoF16 ? launch_conv3x3_wino_f16 : f4 ? launch_conv3x3_winof4 : tail ? launch_conv3x3_wino4s : e->plan.kind == TowerKind::Wino4 ? launch_conv3x3_wino4 : launch_conv3x3_wino;
         auto conv = [&](const ConvLayer& c, const float* in, const float* res, float* out) {
             hipEvent_t s0 = ev(), s1 = ev();
             launch(in, c.w.p, c.b.as<float>(), res, out, nb, FP, FP, st, s0, s1, e->conv_opts.saturated);
@@ -961,6 +969,7 @@ int enqueue_forward(cattus_eval* e, Lane& L, const uint64_t* d_planes, uint32_t 
         case TowerKind::Wino16:
         case TowerKind::Wino4:
         case TowerKind::WinoF4:
+        case TowerKind::WinoF16:
             if (int rc = f.wino()) return rc;
             f.heads_mfma(f.a);
             break;
@@ -1279,6 +1288,7 @@ CATTUS_API const char* cattus_hip_tower_kernel(const cattus_eval* e) {
         case TowerKind::Wino16: return "conv3x3_wino_kernel";
         case TowerKind::Wino4: return one_launch_now(e, e->bpad) ? "tower_wino4_kernel" : "conv3x3_wino4_kernel";
         case TowerKind::WinoF4: return "conv3x3_winof4_kernel";
+        case TowerKind::WinoF16: return "conv3x3_wino_f16_kernel";
         case TowerKind::DirectSplitK: return "conv3x3_splitk_kernel";
         case TowerKind::PerLayer: break;
     }
@@ -1372,6 +1382,18 @@ int resolve_plan(const cattus_net_desc& d, const cattus_eval_config& cfg, const 
     const bool simple = d.filters == 0, tuned = !simple && d.vhc + d.phc <= 32 && !sw.starts("CATTUS_FORCE_GENERIC", '1');
     if (!tuned && act != Act::F32)
         return fail(CATTUS_E_UNSUPPORTED, "bf16 / f16 / f16x2 need the MFMA tower: value + policy head channels <= 32 (got %u + %u)", d.vhc, d.phc);
+    // dtype f16w: the single-term f16 Winograd tower and nothing else -- AUTO and WINOGRAD both mean it, every other form and every
+    // shape it does not cover is refused (never other bits under this name); a SimpleTwoHeadedModel runs in f32 as under every dtype
+    if (cfg.dtype == CATTUS_DTYPE_F16W && !simple) {
+        if (cfg.tower_form != CATTUS_TOWER_AUTO && cfg.tower_form != CATTUS_TOWER_WINOGRAD)
+            return fail(CATTUS_E_UNSUPPORTED, "dtype f16w is the Winograd F(2x2, 3x3) form: tower_form AUTO or WINOGRAD (got %u)", cfg.tower_form);
+        if (!(d.blocks > 0 && wino_f16_supported(bpad, fpad, fpad, d.board)))
+            return fail(CATTUS_E_UNSUPPORTED, "dtype f16w needs an 8x8 board, at least one residual block and a multiple of 64 filters (at least 128)");
+        *plan = TowerPlan();
+        plan->kind = TowerKind::WinoF16;
+        plan->inplace = !sw.starts("CATTUS_WINO_INPLACE", '0');
+        return CATTUS_OK;
+    }
     // the 4-frequency kernel wherever it covers the layer shape (filters a multiple of 64), else the 16-frequency one (128)
     const char* wk = sw.get("CATTUS_WINO_KERNEL");
     if (wk && strcmp(wk, "k16") != 0 && strcmp(wk, "k4") != 0) return fail(CATTUS_E_INVALID, "CATTUS_WINO_KERNEL is k16 or k4");
@@ -1444,7 +1466,8 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
     if ((uint64_t)cfg->plane_words * 64 < (uint64_t)d.board * d.board || cfg->plane_words > 2)
         return fail(CATTUS_E_INVALID, "plane_words %u cannot hold a %ux%u board", cfg->plane_words, d.board, d.board);
     if (d.planes * cfg->plane_words > 128) return fail(CATTUS_E_UNSUPPORTED, "more than 128 plane words per leaf");
-    if (cfg->dtype != CATTUS_DTYPE_F32 && cfg->dtype != CATTUS_DTYPE_BF16 && cfg->dtype != CATTUS_DTYPE_F16X2 && cfg->dtype != CATTUS_DTYPE_F16)
+    if (cfg->dtype != CATTUS_DTYPE_F32 && cfg->dtype != CATTUS_DTYPE_BF16 && cfg->dtype != CATTUS_DTYPE_F16X2 && cfg->dtype != CATTUS_DTYPE_F16 &&
+        cfg->dtype != CATTUS_DTYPE_F16W)
         return fail(CATTUS_E_INVALID, "unknown dtype %u", cfg->dtype);
     if (!simple && (size_t)d.phc * d.board * d.board * 8 * 4 > 64 * 1024) return fail(CATTUS_E_UNSUPPORTED, "policy head too wide for the FC kernel");
 
@@ -1497,7 +1520,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
     e->act = simple ? Act::F32
              : cfg->dtype == CATTUS_DTYPE_BF16 ? Act::BF16
              : cfg->dtype == CATTUS_DTYPE_F16X2 ? Act::F16S
-             : cfg->dtype == CATTUS_DTYPE_F16 ? Act::F16
+             : cfg->dtype == CATTUS_DTYPE_F16 || cfg->dtype == CATTUS_DTYPE_F16W ? Act::F16  // f16w: the direct f16 stem; resolve_plan chooses its tower
                                               : Act::F32;
     // the tuned towers' layout: whole workgroups of boards, filters in whole 64-channel groups (zero channels), the planes in whole
     // 128-byte rows; the other towers pad nothing
@@ -1524,7 +1547,9 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
         // the Winograd tower's hot set in one block: U of every layer, then the lanes' activation buffers (DevArena)
         auto page = [](size_t b) { return (b + 4095) & ~(size_t)4095; };
         const size_t FPz = e->fpad;
-        const size_t u_bytes = page(e->plan.kind == TowerKind::WinoF4 ? winof4_u_elems(e->fpad, e->fpad) * 2 : ((size_t)16 * FPz * FPz * 2 + (size_t)WINO_RING_STAGES * 1024) * 2);
+        const size_t u_bytes = page(e->plan.kind == TowerKind::WinoF4    ? winof4_u_elems(e->fpad, e->fpad) * 2
+                                    : e->plan.kind == TowerKind::WinoF16 ? wino_f16_u_elems(e->fpad, e->fpad) * 2
+                                                                         : ((size_t)16 * FPz * FPz * 2 + (size_t)WINO_RING_STAGES * 1024) * 2);
         const size_t act_bytes_ = page((size_t)e->bpad * e->slots * FPz * 4);
         const size_t want = 2 * (size_t)d.blocks * u_bytes + (size_t)NLANES * (e->plan.inplace ? 2 : 3) * act_bytes_ + (1u << 20);
         void* base = nullptr;
@@ -1610,7 +1635,7 @@ int create_calibrated_impl(const void* weights, size_t nbytes, const cattus_eval
     uint32_t filters = 0;  // 0: SimpleTwoHeadedModel (or no blob at all, which create_impl refuses)
     if (nbytes >= HEADER_BYTES) memcpy(&filters, (const char*)weights + 8 + 5 * 4, 4);
     // only the f16 towers shift their stream: everything else is cattus_hip_create
-    if ((cfg->dtype != CATTUS_DTYPE_F16X2 && cfg->dtype != CATTUS_DTYPE_F16) || filters == 0) return create_impl(weights, nbytes, cfg, switches, out);
+    if ((cfg->dtype != CATTUS_DTYPE_F16X2 && cfg->dtype != CATTUS_DTYPE_F16 && cfg->dtype != CATTUS_DTYPE_F16W) || filters == 0) return create_impl(weights, nbytes, cfg, switches, out);
     cattus_eval_config mcfg{};
     mcfg.struct_size = sizeof mcfg, mcfg.device = cfg->device, mcfg.max_batch = std::min(n, 256u), mcfg.plane_words = cfg->plane_words;
     mcfg.dtype = CATTUS_DTYPE_F32, mcfg.flush_us = cfg->flush_us, mcfg.tower_form = CATTUS_TOWER_AUTO;

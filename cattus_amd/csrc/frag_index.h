@@ -19,5 +19,12 @@ inline size_t wino_frag_index(uint32_t f, uint32_t co, uint32_t ci, uint32_t par
     const uint32_t nst = cin_pad / 16 * 16, stage = (ci >> 4) * 16 + f, lane = ((ci >> 3) & 1) * 32 + (co & 31);
     return ((((size_t)(co >> 5) * nst + stage) * 2 + part) * 64 + lane) * 8 + (ci & 7);
 }
+// K1wh (dtype f16w): element index of the single f16 U (frequency f, output channel co, input channel ci): K1w's order without the lo
+// part -- [cout / 32][k-step x 16 + f][lane][8 f16], 1 KiB per stage; the kernel reads nothing past a cout block's last stage
+inline size_t wino_f16_frag_index(uint32_t f, uint32_t co, uint32_t ci, uint32_t cin_pad) {
+    const uint32_t nst = cin_pad / 16 * 16, stage = (ci >> 4) * 16 + f, lane = ((ci >> 3) & 1) * 32 + (co & 31);
+    return (((size_t)(co >> 5) * nst + stage) * 64 + lane) * 8 + (ci & 7);
+}
+inline size_t wino_f16_u_elems(uint32_t cout_pad, uint32_t cin_pad) { return (size_t)16 * cout_pad * cin_pad; }
 
 }  // namespace cattus

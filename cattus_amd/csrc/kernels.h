@@ -128,6 +128,17 @@ void launch_conv3x3_wino4s(const float* in, const void* wu, const float* bias, c
                            uint32_t cout, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, unsigned* sat);
 hipError_t prepare_wino4s();
 
+// ---- K1wh: the SINGLE-TERM f16 conv in Winograd F(2x2, 3x3) form (dtype f16w; kernels_wino_f16.hip; wino_f16_rule.h has its geometry) ----
+// The arguments of launch_conv3x3_wino4s: in / res / out plain f32 rows on 8x8 boards, res may be out; wu = f16(U 2^s) alone in the order
+// of wino_f16_frag_index (weight_layout.h: wino_u_f16; nothing is read past it); bias = [cout biases | cout inverse scales] of that
+// scaling.  V = B^T d B in f32, rounded once to f16; one MFMA term per product, f32 accumulation, k ascending; outputs capped at
+// WINO_ACT_MAX, sat counts the threads that wrote the cap.  Workgroup = 2 boards x 32 or 64 couts (wf16_ncb; the same bits either way),
+// one launch per layer, no cross-workgroup synchronisation.  bpad % 2 == 0, cin and cout multiples of 64 >= 128.
+bool wino_f16_supported(uint32_t bpad, uint32_t cin, uint32_t cout, uint32_t S);
+void launch_conv3x3_wino_f16(const float* in, const void* wu, const float* bias, const float* res, float* out, uint32_t bpad, uint32_t cin,
+                             uint32_t cout, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, unsigned* sat);
+hipError_t prepare_wino_f16();
+
 // ---- K1sk: the direct split-precision layer with the K walk divided over the waves of a workgroup (kernels_splitk.hip; splitk_rule.h has the
 // split, the reduction order, the grid map and the LDS plan) ----
 // The arguments of launch_conv3x3_mfma's Act::F16S layer with CONV_W_FRAG: in / res / out rows of (hi, lo) pairs on 64-slot boards (S <= 8), wf

@@ -625,6 +625,7 @@ __global__ void __launch_bounds__(256 + 64 * NLOAD, (4 + NLOAD) / 4)
 #pragma unroll
                 for (int j = 0; j < 8; j++) y[j] = valid && v[j] > 0.0f ? v[j] : 0.0f;
                 if (flags & CONV_OUT_F32) {  // the tower's last layer: plain f32 rows for the head kernels
+                    if (flags & CONV_WINO_IN) cap_wino_input(y, valid, sat);  // the stem of the f16 Winograd tower (K1wh): capped and counted
                     float* of = reinterpret_cast<float*>(out) + off;
                     if constexpr (CB == 1) {
                         reinterpret_cast<f32x4*>(of)[0] = *reinterpret_cast<f32x4*>(y);
@@ -1848,7 +1849,7 @@ hipError_t prepare_device() {
     conv_opt_in<ConvSplit>(err);
     conv_opt_in<ConvSplitW>(err);
     for_each_tower64([&](auto kernel, int lds, auto...) { lds_opt_in(err, kernel, lds); });
-    for (hipError_t e : {prepare_tower64_split(), prepare_wino(), prepare_wino4(), prepare_winof4(), prepare_wino4s(), prepare_splitk()})
+    for (hipError_t e : {prepare_tower64_split(), prepare_wino(), prepare_wino4(), prepare_winof4(), prepare_wino4s(), prepare_wino_f16(), prepare_splitk()})
         if (err == hipSuccess) err = e;
     return err;
 }

@@ -92,12 +92,26 @@ inline std::vector<int> stream_shifts(const std::vector<double>& s2, double ceil
 // stream_shift_global(s2_measured).
 // `headroom`: the F(4x4, 3x3) form passes a quarter of ITS cap (WINOF4_CAL_HEADROOM below).
 constexpr double STREAM_CAL_HEADROOM = 4096.0;
-inline std::vector<int> calibrated_stream_shifts(const std::vector<double>& s2_measured, const std::vector<double>& abs_max,
-                                                 double headroom = STREAM_CAL_HEADROOM) {
-    std::vector<int> tk = stream_shifts(s2_measured);
+// the headroom guard alone, on shifts from anywhere
+inline std::vector<int> guarded_stream_shifts(std::vector<int> tk, const std::vector<double>& abs_max, double headroom = STREAM_CAL_HEADROOM) {
     for (size_t k = 0; k < tk.size() && k < abs_max.size(); k++)
         while (tk[k] > 0 && ldexp(abs_max[k], tk[k]) > headroom) tk[k]--;
     return tk;
+}
+inline std::vector<int> calibrated_stream_shifts(const std::vector<double>& s2_measured, const std::vector<double>& abs_max,
+                                                 double headroom = STREAM_CAL_HEADROOM) {
+    return guarded_stream_shifts(stream_shifts(s2_measured), abs_max, headroom);
+}
+// The single-term f16 Winograd tower (dtype f16w) keeps its stream in F32: a lift by 2^t commutes with every operation of it -- the rows,
+// the one rounding of V = B^T d B and of U to 11 bits, the f32 sums -- as long as V stays a normal f16 number, and V's subnormal spacing
+// (2^-24) stays below its ordinary rounding (rms 2^-12) for any channel whose rms is above 2^-12.  A measured lift therefore buys this
+// tower nothing (measured: lifting a seeded network's stream by 2^3 .. 2^7 moved 29 of 15,040 logits, by at most 3e-8) and costs room
+// under the cap.  What measurement does give it is the GUARD: calibrated, the tower runs the estimate's shifts (stream_shifts of the
+// BatchNorm sums, as without calibration), each lowered while the channel's measured largest |value| 2^t_k exceeds the headroom.  A
+// network whose estimate is right -- every seeded one -- keeps its shifts and its bits.
+inline std::vector<int> calibrated_stream_shifts_f32_stream(const std::vector<int>& estimate, const std::vector<double>& abs_max,
+                                                            double headroom = STREAM_CAL_HEADROOM) {
+    return guarded_stream_shifts(estimate, abs_max, headroom);
 }
 constexpr double WINOF4_CAL_HEADROOM = WINOF4_ACT_MAX / 4;  // 163.75
 // The F(4x4, 3x3) form's ceiling on the estimate path (stream_shifts' `ceiling`), where there is no abs_max to guard with.  2: a
@@ -199,6 +213,15 @@ inline std::vector<_Float16> wino_u(const std::vector<double>& U, const ConvShap
         for (uint32_t ci = 0; ci < s.cin; ci++)
             for (uint32_t q = 0; q < 16; q++)
                 split_f16((float)ldexp(U[((size_t)co * s.cin + ci) * 16 + q], shift[co]), wu[wino_frag_index(q, co, ci, 0, s.cin_pad)], wu[wino_frag_index(q, co, ci, 1, s.cin_pad)]);
+    return wu;
+}
+// f16(U 2^s) alone, in the single-term f16 Winograd kernel's fragment order (dtype f16w; wino_f16_frag_index): half of wino_u's bytes
+inline std::vector<_Float16> wino_u_f16(const std::vector<double>& U, const ConvShape& s, const std::vector<int>& shift) {
+    std::vector<_Float16> wu(wino_f16_u_elems(s.cout_pad, s.cin_pad), (_Float16)0.0f);
+    for (uint32_t co = 0; co < s.cout; co++)
+        for (uint32_t ci = 0; ci < s.cin; ci++)
+            for (uint32_t q = 0; q < 16; q++)
+                wu[wino_f16_frag_index(q, co, ci, s.cin_pad)] = (_Float16)(float)ldexp(U[((size_t)co * s.cin + ci) * 16 + q], shift[co]);
     return wu;
 }
 

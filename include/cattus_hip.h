@@ -49,6 +49,28 @@ typedef enum cattus_dtype {
      * of two), f32 accumulation, f32 heads.  A throughput mode like bf16 -- same MFMA count and kernel -- with three more
      * significand bits; outside the reference's cross-runtime tolerance (DESIGN.md section 4 for what it does to a search). */
     CATTUS_DTYPE_F16 = 3,
+    /* Single-term f16 in Winograd F(2x2, 3x3) form with an f32 stream: the stem on the direct f16 kernel, every layer behind it as
+     * Y = A^T [sum_k U V] A with U = f16(G g G^T 2^s) and V = f16(B^T d B) (V made in f32 and rounded once), one f16 MFMA term per
+     * product, f32 accumulation, and PLAIN F32 rows between the layers: the residual stream is never rounded to 11 bits.  2.25x fewer
+     * MFMAs than CATTUS_DTYPE_F16; in emulation about twice as close to a float64 run of the network as that tower from two blocks
+     * up (profiles/winograd_gate_f16w.json; device figures: profiles/f16w_numerics.txt).  Bits of its own.
+     * Coverage: the Winograd form's -- an 8x8 board, at least one residual block, a multiple of 64 filters >= 128, vhc + phc <= 32;
+     * anything else returns CATTUS_E_UNSUPPORTED, never other bits under this name.  Activations are capped at 16,376 (a transformed
+     * input is a signed sum of four and must stay inside the f16 range) and counted in cattus_stats.saturated.
+     * tower_form: AUTO and WINOGRAD both mean this form; DIRECT, WINOGRAD_F4 and DIRECT_SPLITK are refused with CATTUS_E_UNSUPPORTED.
+     * tail_leaves is ignored (cattus_hip_tail_leaves reports 0).  A SimpleTwoHeadedModel blob runs in f32, as under every dtype.
+     * cattus_hip_create_calibrated: the stream is f32, so a measured lift buys nothing here; the tower keeps the shifts of the BatchNorm
+     * estimate and takes from the sample only the headroom guard (a channel's shift is lowered while its measured largest |value| 2^t
+     * exceeds 4096, a quarter of the cap).  A network whose estimate is right keeps its shifts and its bits.
+     * Measured, first build (scripts/f16w_time.py -> profiles/f16w_first_build.txt; one process, the towers alternating; chess 20x256, ms
+     * per step at 64 / 128 / 256 leaves): F16W 0.50 / 0.68 / 1.24, F16 0.35 / 0.55 / 0.87, F16X2 in Winograd form (one launch) 0.89 /
+     * 0.90 / 1.17; chess 4x128 at 256 leaves 0.116 / 0.097 / 0.152.  So it is 1.2 - 1.45x SLOWER than CATTUS_DTYPE_F16 at every size
+     * measured, where 12 % is what two boxes differ by: NOT recommended for speed.  What it buys is F16's operand width at about half
+     * F16's error (device: rms |dlogit| against float64 0.58x on the 4x128 fixture, 0.45x on the 20x256 one), and up to 128 leaves
+     * 0.55 - 0.75x the step time of F16X2's Winograd form -- at 11 significant bits where that tower has 22.  Search level (256
+     * searches of 800 simulations on chess 20x256 against the f32 search): 99.6 % of the moves equal, visit L1 mean 0.00037; F16 on the
+     * same searches 99.2 %, 0.00039.  No counter or stamped run of the kernel was made: what its loop is bound by is not measured. */
+    CATTUS_DTYPE_F16W = 4,
 } cattus_dtype;
 /* Every dtype takes any network the blob format and the plane pack allow: up to 128 plane words per leaf (planes x plane_words),
  * e.g. AlphaZero's 119 chess planes. */
