@@ -339,6 +339,10 @@ enum class TowerKind {
     // Winograd F(2x2, 3x3) form with ONE f16 term per product and f32 rows between the layers (kernels_wino_f16.hip); bits of its own,
     // activations capped at WINO_ACT_MAX, always one launch per layer
     WinoF16,
+    // dtype f32w (Act::F32 with this kind, and no other kind for that dtype): the stem on the direct f32 kernel with the exact tower's bits,
+    // every layer behind it in Winograd F(2x2, 3x3) form with f32 operands on the f32 tower's own rows (kernels_wino_f32.hip); bits of its
+    // own, no cap, no stream shift, no saturation counter, always one launch per layer
+    WinoF32,
     // f16x2, 64-slot boards, 128 .. SK_MAX_FILTERS filters: the per-layer direct tower with the K walk of every layer behind the stem divided
     // over the waves of a workgroup (kernels_splitk.hip), for batches of a few leaves: only for tower_form DIRECT_SPLITK, never by AUTO; its
     // f32 summation order, and so its bits, are its own; rows in the direct form's layout
@@ -352,7 +356,7 @@ struct TowerPlan {
     // a layer has more tiles than the device has CUs (CATTUS_WINO_PERSIST=0: per-layer launches) -- for the batches one_launch_now() admits
     bool one_launch = false;
     bool tuned() const { return kind != TowerKind::Simple && kind != TowerKind::Generic; }  // the MFMA NHWC towers
-    bool wino() const { return kind == TowerKind::Wino16 || kind == TowerKind::Wino4 || kind == TowerKind::WinoF4 || kind == TowerKind::WinoF16; }  // f32 rows between the layers
+    bool wino() const { return kind == TowerKind::Wino16 || kind == TowerKind::Wino4 || kind == TowerKind::WinoF4 || kind == TowerKind::WinoF16 || kind == TowerKind::WinoF32; }  // f32 rows between the layers
 };
 
 }  // namespace
@@ -519,9 +523,11 @@ int upload_conv(cattus_eval* e, ConvLayer& L, const Folded& f, uint32_t cout, ui
         return up(L.w, winof4_u(U, s, sh), &e->arena);
     }
     if (e->plan.wino() && !stem) {
-        std::vector<int> sh;
+        std::vector<int> sh;  // wino_transform's per-channel scale: the f16 kinds' (WinoF32 takes U unscaled and the biases alone)
         const std::vector<double> U = wino_transform(f, s, &sh);
-        if ((rc = up(L.b, bias_and_scales(f, s, &sh)))) return rc;
+        const bool f32w = e->plan.kind == TowerKind::WinoF32;
+        if ((rc = up(L.b, bias_and_scales(f, s, f32w ? nullptr : &sh)))) return rc;
+        if (f32w) return up(L.w, wino_u_f32(U, s), &e->arena);
         if (e->plan.kind == TowerKind::WinoF16) return up(L.w, wino_u_f16(U, s, sh), &e->arena);
         return up(L.w, wino_u(U, s, sh), &e->arena);
     }
@@ -887,10 +893,12 @@ struct Forward {
         return a;
     }
 
-    // Wino16 / Wino4 / WinoF4 / WinoF16: the stem on the direct kernel (the split one, or the f16 one under dtype f16w), every layer behind it in Winograd form, f32 rows between the layers
+    // Wino16 / Wino4 / WinoF4 / WinoF16 / WinoF32: the stem on the direct kernel (the split one, the f16 one under dtype f16w, the f32 one under f32w),
+    // every layer behind it in Winograd form, f32 rows between the layers
     int wino() {
-        const bool f4 = e->plan.kind == TowerKind::WinoF4;
-        conv_mfma(e->stem, L.x0.p, nullptr, a, CONV_OUT_F32 | (f4 ? CONV_WINOF4_IN : CONV_WINO_IN), true);
+        const bool f4 = e->plan.kind == TowerKind::WinoF4, f32w = e->plan.kind == TowerKind::WinoF32;
+        // (the f32 stem takes no flag: conv3x3_mfma_v2_kernel<float> writes plain f32 [row][cout] rows on 64-slot boards, the Winograd form's layout, and reads no flag)
+        conv_mfma(e->stem, L.x0.p, nullptr, a, f32w ? 0 : CONV_OUT_F32 | (f4 ? CONV_WINOF4_IN : CONV_WINO_IN), true);
         seen(0, a, tower_source(0));
         const bool tail = !obs && e->tail_leaves && n <= e->tail_leaves;  // a short batch: the small-tile kernel, one launch per layer
         if (tail && !tt) e->tail_batches.fetch_add(1, std::memory_order_relaxed);  // (a timing pass is not a batch)
@@ -908,7 +916,7 @@ struct Forward {
             HIP_TRY(hipMemcpyAsync(L.h_tower_err.p, tower_err, 4, hipMemcpyDeviceToHost, st));
             return CATTUS_OK;
         }
-        const auto launch = e->plan.kind == TowerKind::WinoF16 ? launch_conv3x3_wino_f16 : f4 ? launch_conv3x3_winof4 : tail ? launch_conv3x3_wino4s : e->plan.kind == TowerKind::Wino4 ? launch_conv3x3_wino4 : launch_conv3x3_wino;
+        const auto launch = f32w ? launch_conv3x3_wino_f32 : e->plan.kind == TowerKind::WinoF16 ? launch_conv3x3_wino_f16 : f4 ? launch_conv3x3_winof4 : tail ? launch_conv3x3_wino4s : e->plan.kind == TowerKind::Wino4 ? launch_conv3x3_wino4 : launch_conv3x3_wino;
         auto conv = [&](const ConvLayer& c, const float* in, const float* res, float* out) {
             hipEvent_t s0 = ev(), s1 = ev();
             launch(in, c.w.p, c.b.as<float>(), res, out, nb, FP, FP, st, s0, s1, e->conv_opts.saturated);
@@ -970,6 +978,7 @@ int enqueue_forward(cattus_eval* e, Lane& L, const uint64_t* d_planes, uint32_t 
         case TowerKind::Wino4:
         case TowerKind::WinoF4:
         case TowerKind::WinoF16:
+        case TowerKind::WinoF32:
             if (int rc = f.wino()) return rc;
             f.heads_mfma(f.a);
             break;
@@ -1289,6 +1298,7 @@ CATTUS_API const char* cattus_hip_tower_kernel(const cattus_eval* e) {
         case TowerKind::Wino4: return one_launch_now(e, e->bpad) ? "tower_wino4_kernel" : "conv3x3_wino4_kernel";
         case TowerKind::WinoF4: return "conv3x3_winof4_kernel";
         case TowerKind::WinoF16: return "conv3x3_wino_f16_kernel";
+        case TowerKind::WinoF32: return "conv3x3_wino_f32_kernel";
         case TowerKind::DirectSplitK: return "conv3x3_splitk_kernel";
         case TowerKind::PerLayer: break;
     }
@@ -1394,6 +1404,18 @@ int resolve_plan(const cattus_net_desc& d, const cattus_eval_config& cfg, const 
         plan->inplace = !sw.starts("CATTUS_WINO_INPLACE", '0');
         return CATTUS_OK;
     }
+    // dtype f32w: the f32-operand Winograd tower and nothing else, by the same rule
+    if (cfg.dtype == CATTUS_DTYPE_F32W && !simple) {
+        if (cfg.tower_form != CATTUS_TOWER_AUTO && cfg.tower_form != CATTUS_TOWER_WINOGRAD)
+            return fail(CATTUS_E_UNSUPPORTED, "dtype f32w is the Winograd F(2x2, 3x3) form: tower_form AUTO or WINOGRAD (got %u)", cfg.tower_form);
+        if (!(tuned && d.blocks > 0 && wino_f32_supported(bpad, fpad, fpad, d.board)))
+            return fail(CATTUS_E_UNSUPPORTED,
+                        "dtype f32w needs an 8x8 board, at least one residual block, a multiple of 64 filters (at least 128) and value + policy head channels <= 32");
+        *plan = TowerPlan();
+        plan->kind = TowerKind::WinoF32;
+        plan->inplace = !sw.starts("CATTUS_WINO_INPLACE", '0');
+        return CATTUS_OK;
+    }
     // the 4-frequency kernel wherever it covers the layer shape (filters a multiple of 64), else the 16-frequency one (128)
     const char* wk = sw.get("CATTUS_WINO_KERNEL");
     if (wk && strcmp(wk, "k16") != 0 && strcmp(wk, "k4") != 0) return fail(CATTUS_E_INVALID, "CATTUS_WINO_KERNEL is k16 or k4");
@@ -1467,7 +1489,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
         return fail(CATTUS_E_INVALID, "plane_words %u cannot hold a %ux%u board", cfg->plane_words, d.board, d.board);
     if (d.planes * cfg->plane_words > 128) return fail(CATTUS_E_UNSUPPORTED, "more than 128 plane words per leaf");
     if (cfg->dtype != CATTUS_DTYPE_F32 && cfg->dtype != CATTUS_DTYPE_BF16 && cfg->dtype != CATTUS_DTYPE_F16X2 && cfg->dtype != CATTUS_DTYPE_F16 &&
-        cfg->dtype != CATTUS_DTYPE_F16W)
+        cfg->dtype != CATTUS_DTYPE_F16W && cfg->dtype != CATTUS_DTYPE_F32W)
         return fail(CATTUS_E_INVALID, "unknown dtype %u", cfg->dtype);
     if (!simple && (size_t)d.phc * d.board * d.board * 8 * 4 > 64 * 1024) return fail(CATTUS_E_UNSUPPORTED, "policy head too wide for the FC kernel");
 
@@ -1521,7 +1543,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
              : cfg->dtype == CATTUS_DTYPE_BF16 ? Act::BF16
              : cfg->dtype == CATTUS_DTYPE_F16X2 ? Act::F16S
              : cfg->dtype == CATTUS_DTYPE_F16 || cfg->dtype == CATTUS_DTYPE_F16W ? Act::F16  // f16w: the direct f16 stem; resolve_plan chooses its tower
-                                              : Act::F32;
+                                              : Act::F32;  // f32w too: the direct f32 stem and f32 rows; resolve_plan chooses its tower
     // the tuned towers' layout: whole workgroups of boards, filters in whole 64-channel groups (zero channels), the planes in whole
     // 128-byte rows; the other towers pad nothing
     e->slots = tower_slots(d.board);
@@ -1549,6 +1571,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
         const size_t FPz = e->fpad;
         const size_t u_bytes = page(e->plan.kind == TowerKind::WinoF4    ? winof4_u_elems(e->fpad, e->fpad) * 2
                                     : e->plan.kind == TowerKind::WinoF16 ? wino_f16_u_elems(e->fpad, e->fpad) * 2
+                                    : e->plan.kind == TowerKind::WinoF32 ? wino_f32_u_elems(e->fpad, e->fpad) * 4
                                                                          : ((size_t)16 * FPz * FPz * 2 + (size_t)WINO_RING_STAGES * 1024) * 2);
         const size_t act_bytes_ = page((size_t)e->bpad * e->slots * FPz * 4);
         const size_t want = 2 * (size_t)d.blocks * u_bytes + (size_t)NLANES * (e->plan.inplace ? 2 : 3) * act_bytes_ + (1u << 20);
@@ -1935,11 +1958,14 @@ CATTUS_API int cattus_hip_stats(cattus_eval* e, cattus_stats* out) {
 
 namespace {
 
+// Act::F32 is the exact tower under dtype f32; dtype f32w runs the same Act on a tower of its own bits, which has a shadow like any other
+bool exact_f32(const cattus_eval* e) { return e->act == Act::F32 && e->plan.kind != TowerKind::WinoF32; }
+
 // What cattus_hip_verify and cattus_hip_trace ask before anything else: is there an exact tower to hold this evaluator to, and is `weights`
 // the blob it was created from (the evaluator keeps no host copy of it)?
 int shadow_args(const cattus_eval* e, const void* weights, size_t nbytes, const char* what) {
     if (e->plan.kind == TowerKind::Simple) return fail(CATTUS_E_UNSUPPORTED, "a SimpleTwoHeadedModel runs in f32 whatever its dtype: there is nothing to %s it against", what);
-    if (e->act == Act::F32) return fail(CATTUS_E_UNSUPPORTED, "a dtype f32 evaluator is the exact tower: its shadow would be itself");
+    if (exact_f32(e)) return fail(CATTUS_E_UNSUPPORTED, "a dtype f32 evaluator is the exact tower: its shadow would be itself");
     if (nbytes != e->blob_bytes || blob_hash64(weights, nbytes) != e->blob_hash)
         return fail(CATTUS_E_INVALID, "%s: this is not the weight blob the evaluator was created from", what);
     return CATTUS_OK;
@@ -2114,7 +2140,7 @@ CATTUS_API int cattus_hip_verify_worst_planes(cattus_eval* e, uint64_t* planes) 
 CATTUS_API int cattus_hip_verify_prior_stats(cattus_eval* e, cattus_prior_stats* out) {
     if (!e || !out) return fail(CATTUS_E_INVALID, "NULL argument");
     if (out->struct_size != sizeof(cattus_prior_stats)) return fail(CATTUS_E_INVALID, "cattus_prior_stats.struct_size mismatch");
-    if (e->plan.kind == TowerKind::Simple || e->act == Act::F32)
+    if (e->plan.kind == TowerKind::Simple || exact_f32(e))
         return fail(CATTUS_E_UNSUPPORTED, "a dtype f32 evaluator and a SimpleTwoHeadedModel have no shadow to compare priors with");
     std::lock_guard<std::mutex> lk(e->stat_mu);
     const PriorStats& s = e->priors;
@@ -2131,7 +2157,7 @@ CATTUS_API int cattus_hip_verify_prior_stats(cattus_eval* e, cattus_prior_stats*
 CATTUS_API int cattus_hip_verify_worst_prior(cattus_eval* e, uint64_t* planes, uint16_t* legal_idx, uint32_t cap, uint32_t* legal_count, uint32_t* top,
                                              uint32_t* top_ref) {
     if (!e || !planes || !legal_idx || !legal_count || !top || !top_ref) return fail(CATTUS_E_INVALID, "NULL argument");
-    if (e->plan.kind == TowerKind::Simple || e->act == Act::F32)
+    if (e->plan.kind == TowerKind::Simple || exact_f32(e))
         return fail(CATTUS_E_UNSUPPORTED, "a dtype f32 evaluator and a SimpleTwoHeadedModel have no shadow to compare priors with");
     std::lock_guard<std::mutex> lk(e->stat_mu);
     const cattus_eval::WorstPrior& w = e->worst_prior;

@@ -26,5 +26,13 @@ inline size_t wino_f16_frag_index(uint32_t f, uint32_t co, uint32_t ci, uint32_t
     return (((size_t)(co >> 5) * nst + stage) * 64 + lane) * 8 + (ci & 7);
 }
 inline size_t wino_f16_u_elems(uint32_t cout_pad, uint32_t cin_pad) { return (size_t)16 * cout_pad * cin_pad; }
+// K1wf (dtype f32w): element index of the f32 U (frequency f, output channel co, input channel ci):
+// [cout / 32][8-channel group x 16 + f][lane][4 f32], 1 KiB per stage, lane = (ci / 4 % 2) * 32 + co % 32 -- the operand piece
+// Mfma<float>::mac takes (device_common.h); the kernel reads nothing past a cout block's last stage: no ring tail
+inline size_t wino_f32_frag_index(uint32_t f, uint32_t co, uint32_t ci, uint32_t cin_pad) {
+    const uint32_t nst = cin_pad / 8 * 16, stage = (ci >> 3) * 16 + f, lane = ((ci >> 2) & 1) * 32 + (co & 31);
+    return (((size_t)(co >> 5) * nst + stage) * 64 + lane) * 4 + (ci & 3);
+}
+inline size_t wino_f32_u_elems(uint32_t cout_pad, uint32_t cin_pad) { return (size_t)16 * cout_pad * cin_pad; }
 
 }  // namespace cattus

@@ -139,6 +139,18 @@ void launch_conv3x3_wino_f16(const float* in, const void* wu, const float* bias,
                              uint32_t cout, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, unsigned* sat);
 hipError_t prepare_wino_f16();
 
+// ---- K1wf: the F32-OPERAND conv in Winograd F(2x2, 3x3) form (dtype f32w; kernels_wino_f32.hip; wino_f32_rule.h has its geometry and its
+// arithmetic order) ----
+// The arguments of launch_conv3x3_wino_f16: in / res / out plain f32 rows on 8x8 boards (the f32 tower's rows), res may be out; wu =
+// f32(G g G^T) without a scale in the order of wino_f32_frag_index (weight_layout.h: wino_u_f32; nothing is read past it); bias = cout
+// biases.  V = B^T d B in f32; one f32 MFMA chain per product (Mfma<float>::mac, 8-channel groups ascending); Y + bias, + skip, ReLU; no
+// cap: the last argument is not read.  Workgroup = 2 boards x 32 or 64 couts (wf32_ncb; the same bits either way), one launch per layer,
+// no cross-workgroup synchronisation.  bpad % 2 == 0, cin and cout multiples of 64 >= 128.
+bool wino_f32_supported(uint32_t bpad, uint32_t cin, uint32_t cout, uint32_t S);
+void launch_conv3x3_wino_f32(const float* in, const void* wu, const float* bias, const float* res, float* out, uint32_t bpad, uint32_t cin,
+                             uint32_t cout, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, unsigned* unused);
+hipError_t prepare_wino_f32();
+
 // ---- K1sk: the direct split-precision layer with the K walk divided over the waves of a workgroup (kernels_splitk.hip; splitk_rule.h has the
 // split, the reduction order, the grid map and the LDS plan) ----
 // The arguments of launch_conv3x3_mfma's Act::F16S layer with CONV_W_FRAG: in / res / out rows of (hi, lo) pairs on 64-slot boards (S <= 8), wf

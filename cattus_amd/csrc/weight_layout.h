@@ -224,6 +224,15 @@ inline std::vector<_Float16> wino_u_f16(const std::vector<double>& U, const Conv
                 wu[wino_f16_frag_index(q, co, ci, s.cin_pad)] = (_Float16)(float)ldexp(U[((size_t)co * s.cin + ci) * 16 + q], shift[co]);
     return wu;
 }
+// f32(U) alone, no scale, in the f32-operand Winograd kernel's fragment order (dtype f32w; wino_f32_frag_index): the float64 transform
+// rounded once
+inline std::vector<float> wino_u_f32(const std::vector<double>& U, const ConvShape& s) {
+    std::vector<float> wu(wino_f32_u_elems(s.cout_pad, s.cin_pad), 0.0f);
+    for (uint32_t co = 0; co < s.cout; co++)
+        for (uint32_t ci = 0; ci < s.cin; ci++)
+            for (uint32_t q = 0; q < 16; q++) wu[wino_f32_frag_index(q, co, ci, s.cin_pad)] = (float)U[((size_t)co * s.cin + ci) * 16 + q];
+    return wu;
+}
 
 // Winograd F(4x4, 3x3) form (winof4_rule.h): U = G g G^T per (cout, cin) in float64, [(co * cin + ci) * 36 + frequency], and one scale
 // per output channel over all 36 frequencies of all its input channels

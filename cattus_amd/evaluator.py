@@ -26,6 +26,10 @@ DTYPE_F32, DTYPE_BF16, DTYPE_F16X2, DTYPE_F16, DTYPE_F16W = 0, 1, 2, 3, 4
 # "f16x2": the split-precision tower (pairs of f16 values, 22 significant bits; include/cattus_hip.h); "f16": single-term f16;
 # "f16w": single-term f16 in Winograd F(2x2,3x3) form with f32 rows between the layers (CATTUS_DTYPE_F16W: opt-in, bits of its own)
 _DTYPES = {"f32": DTYPE_F32, "bf16": DTYPE_BF16, "f16x2": DTYPE_F16X2, "f16": DTYPE_F16, "f16w": DTYPE_F16W}
+# "f32w": f32 operands in Winograd F(2x2,3x3) form on the f32 tower's rows (CATTUS_DTYPE_F32W: opt-in, bits of its own).  A table of its own
+# beside _DTYPES, which stays the five dtypes it was; the constructor consults both.
+DTYPE_F32W = 5
+_DTYPES_WINO_F32 = {"f32w": DTYPE_F32W}
 
 # every symbol include/cattus_hip.h declares
 ABI_SYMBOLS = [
@@ -329,14 +333,16 @@ class HipEvaluator:
         verify_every: int = 0,
         tail_leaves: int = 0,
     ):
-        """dtype: "f32" | "bf16" | "f16x2" | "f16" | "f16w" (cattus_dtype).  "f16w" is the single-term f16 tower in Winograd F(2x2,3x3) form with an f32 stream: an 8x8
+        """dtype: "f32" | "bf16" | "f16x2" | "f16" | "f16w" | "f32w" (cattus_dtype).  "f16w" is the single-term f16 tower in Winograd F(2x2,3x3) form with an f32 stream: an 8x8
         board, at least one residual block, a multiple of 64 filters >= 128, tower_form "auto" or "winograd" (both mean it); anything else is refused.
+        "f32w" is the f32-operand tower in the same form with the same coverage and the same refusals: the exact tower's stem, U = f32(G g G^T), f32 sums, no
+        cap, no stream shift, ``saturated`` stays 0; bits of its own (not the exact tower's); ``verify`` / ``trace`` hold it to the f32 shadow like any other.
         tower_form: "auto" | "direct" | "winograd" | "winograd_f4" | "direct_splitk" (cattus_tower_form; None = "auto", or what CATTUS_WINOGRAD=0/1 in the
         environment says; "winograd_f4", the F(4x4,3x3) form, and "direct_splitk", the direct form with the K walk divided over a workgroup's waves
         for batches of a few leaves, are opt-in only: never what "auto" picks, and each has bits of its own).  switches: diagnostic switches for cattus_hip_create_diag (None = the CATTUS_* ones found in the
         environment, {} = none).  calibration: sample positions, uint64 ``[n, C, plane_words]`` -- the f16 / f16x2 towers then
         take their stream shifts from the range measured on them instead of from the BatchNorm parameters
-        (cattus_hip_create_calibrated; nothing to calibrate for f32 / bf16, which come out as without it; "f16w", whose stream is f32, keeps the
+        (cattus_hip_create_calibrated; nothing to calibrate for f32 / bf16, which come out as without it, and nothing for "f32w"; "f16w", whose stream is f32, keeps the
         BatchNorm estimate's shifts and takes only the headroom guard from the sample).  verify_every: N >= 1
         checks every Nth batch against a shadow f32 tower (``verify``); 0, the default, builds no shadow and checks nothing.
         tail_leaves: k >= 1 runs batches of at most k leaves of the Winograd F(2x2,3x3) tower on its small-tile kernel (cattus_eval_config.tail_leaves:
@@ -353,12 +359,12 @@ class HipEvaluator:
             tower_form = "auto" if not legacy else ("winograd" if legacy[0] == "1" else "direct")
             if tower_form == "winograd" and not (dtype == "f16x2" and self.desc.board == 8 and self.desc.blocks > 0 and self.desc.filters >= 128 and self.desc.filters % 64 == 0):
                 tower_form = "auto"  # the environment form was a wish ("where the shape allows it"); the config field is a demand
-            if dtype == "f16w":
+            if dtype in ("f16w", "f32w"):
                 tower_form = "auto"  # the dtype is its form: the environment's wish for the f16x2 tower does not reach it
         if switches is None:
             switches = {k: os.environ[k] for k in DIAG_SWITCHES if k in os.environ}
         self.tower_form = tower_form
-        cfg = EvalConfig(C.sizeof(EvalConfig), device, self.batch_size, self.plane_words, _DTYPES[dtype], flush_us, TOWER_FORMS[tower_form], int(tail_leaves))
+        cfg = EvalConfig(C.sizeof(EvalConfig), device, self.batch_size, self.plane_words, {**_DTYPES, **_DTYPES_WINO_F32}[dtype], flush_us, TOWER_FORMS[tower_form], int(tail_leaves))
         h = C.c_void_p()
         buf = C.create_string_buffer(blob, len(blob))
         text = ";".join(f"{k}={v}" for k, v in switches.items()).encode() if switches else None

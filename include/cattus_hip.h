@@ -71,6 +71,30 @@ typedef enum cattus_dtype {
      * searches of 800 simulations on chess 20x256 against the f32 search): 99.6 % of the moves equal, visit L1 mean 0.00037; F16 on the
      * same searches 99.2 %, 0.00039.  No counter or stamped run of the kernel was made: what its loop is bound by is not measured. */
     CATTUS_DTYPE_F16W = 4,
+    /* F32 operands in Winograd F(2x2, 3x3) form on the f32 tower's own rows: the stem on the direct f32 kernel, unchanged and with
+     * CATTUS_DTYPE_F32's bits; every layer behind it as Y = A^T [sum_k U V] A with U = f32(G g G^T) (the host's float64 transform
+     * rounded once, no per-channel scale) and V = B^T d B made in f32, one f32 MFMA term per product, f32 accumulation, plain f32 rows
+     * between the layers, the common f32 heads.  2.25x fewer MFMAs than CATTUS_DTYPE_F32, whose kernel is MFMA-bound.  No cap, no
+     * stream shift, no saturation counter: cattus_stats.saturated stays 0 and values behave as under CATTUS_DTYPE_F32 (non-finite logits
+     * are scrubbed by the heads as everywhere).  Bits of its own: another f32 summation order of other f32 operands than the exact
+     * tower's, NOT that tower's bits -- but, like that tower's, an in-order fmaf chain that a CPU restatement reproduces bit for bit
+     * (csrc/wino_f32_rule.h, tests/wino_f32_layer_ref.cpp).  cattus_hip_verify / _trace hold it to the f32 shadow like any other dtype.
+     * Coverage: CATTUS_DTYPE_F16W's -- an 8x8 board, at least one residual block, a multiple of 64 filters >= 128, vhc + phc <= 32;
+     * anything else returns CATTUS_E_UNSUPPORTED, never other bits under this name.  tower_form: AUTO and WINOGRAD both mean this form;
+     * DIRECT, WINOGRAD_F4 and DIRECT_SPLITK are refused with CATTUS_E_UNSUPPORTED.  tail_leaves is ignored (cattus_hip_tail_leaves reports
+     * 0).  A SimpleTwoHeadedModel blob runs in f32, as under every dtype.  cattus_hip_create_calibrated has nothing to calibrate: it
+     * validates planes and n and is then cattus_hip_create.  cattus_hip_stream_range stays CATTUS_E_UNSUPPORTED (it measures on the exact
+     * per-layer tower only).
+     * Measured, first build (scripts/f32w_time.py -> profiles/f32w_first_build.txt; one process, the towers alternating; chess 20x256, ms
+     * per step at 64 / 128 / 256 leaves): F32W 1.120 / 1.917 / 3.722, F32 1.646 / 3.101 / 5.701, F16X2 in Winograd form (one launch) 0.894 / 0.895 /
+     * 1.189; chess 4x128 at 256 leaves 0.245 / 0.365 / 0.151.  So it is 1.47 - 1.62x FASTER than CATTUS_DTYPE_F32 at every size measured, where
+     * 12 % is what two boxes differ by: RECOMMENDED over F32 from 64 leaves on where the coverage holds and F32's own bits are not needed.  68.8 k node-evals/s at 256 leaves
+     * (F32: 44.9 k).  The estimate of ~55 us per 256 -> 256 layer was missed: 89.4 us per launch.  Per leaf (profiles/f32w_numerics.txt): inside
+     * the reference's cross-runtime bar on both fixtures, rms |dlogit| against float64 0.80x / 0.54x F32's.  Search level (256 searches of
+     * 800 simulations on chess 20x256 against the f32 search): 100.0 % of the moves equal, visit L1 mean 0.  Not measured: batches
+     * below 64 leaves, other filter counts than 128 and 256; no counter or stamped run of the kernel was made: what binds its loop is
+     * a supposition. */
+    CATTUS_DTYPE_F32W = 5,
 } cattus_dtype;
 /* Every dtype takes any network the blob format and the plane pack allow: up to 128 plane words per leaf (planes x plane_words),
  * e.g. AlphaZero's 119 chess planes. */
