@@ -325,6 +325,7 @@ enum class TowerKind {
     Generic,     // NCHW f32 SIMT tower: heads wider than one 32-row MFMA tile, or the checker (CATTUS_FORCE_GENERIC=1)
     PerLayer,    // MFMA NHWC tower, one launch per conv layer (any dtype)
     Resident64,  // bf16, <= 64 filters: the whole tower in one launch, activations resident in LDS (tower64_lds_kernel; CATTUS_TOWER64=0: PerLayer)
+                 // Act::F16 with this kind: the same launch with the per-layer f16 tower's bits, only for tower_form RESIDENT, never by AUTO
     Resident64Split,  // f16x2, <= 64 filters: the same in split precision (tower64_split_kernel; weights from the register ring)
     // f16x2, 8x8 boards: every layer behind the stem in Winograd F(2x2, 3x3) form, for max_batch > 128 (up to there the direct kernels'
     // small tiles win or tie -- whole step of chess 20x256, direct | Winograd: 0.59 | 0.89 ms at 64 leaves, 0.87 | 0.89 at 96, 0.97 | 0.90 at
@@ -828,15 +829,19 @@ struct Forward {
         ta.hv_pol = hv_leaves(e) * e->kvp, ta.kvp = e->kvp, ta.kpp = e->kpp, ta.vhc = d.vhc, ta.ocn = d.vhc + d.phc;
     }
 
-    void resident64() {
+    // bf16: the head convs fused, nullptr; f16: the tower's output as plain f32 rows in `a` for the f32 head kernels
+    const void* resident64() {
         Tower64Args ta{};
-        resident_args(ta, true);
+        const bool f16 = e->act == Act::F16;
+        resident_args(ta, !f16);
+        if (f16) ta.out = a, ta.sat = e->conv_opts.saturated;
         const uint32_t rows = nb * e->slots;
         // 128-row workgroups; for 64-slot boards one board per workgroup while that leaves no CU with two of them
         hipEvent_t s0 = ev(), s1 = ev();
         int ch = e->slots == 64 && rows / 64 <= 256 ? 4 : 2;
         if (e->t64_force_ch) ch = e->t64_force_ch == 4 && e->slots == 64 ? 4 : 2;  // A/B runs, the row-split test
-        launch_tower64(ta, rows, ch, e->t64_layer_steps, st, s0, s1);
+        launch_tower64(e->act, ta, rows, ch, e->t64_layer_steps, st, s0, s1);
+        return f16 ? ta.out : nullptr;
     }
 
     // CATTUS_T64S_HEADS=0: the tower's output as plain f32 rows in `a` for the f32 head kernels
@@ -972,7 +977,7 @@ int enqueue_forward(cattus_eval* e, Lane& L, const uint64_t* d_planes, uint32_t 
         case TowerKind::Generic: f.heads_generic(f.generic()); break;
         case TowerKind::PerLayer: f.heads_mfma(f.per_layer()); break;
         case TowerKind::DirectSplitK: f.heads_mfma(f.per_layer()); break;  // the stem through conv_mfma, every layer behind it through conv_splitk
-        case TowerKind::Resident64: f.resident64(), f.heads_mfma(nullptr); break;
+        case TowerKind::Resident64: f.heads_mfma(f.resident64()); break;
         case TowerKind::Resident64Split: f.heads_mfma(f.resident64_split()); break;
         case TowerKind::Wino16:
         case TowerKind::Wino4:
@@ -1440,6 +1445,15 @@ int resolve_plan(const cattus_net_desc& d, const cattus_eval_config& cfg, const 
         return CATTUS_OK;
     }
     const bool resident = tuned && fpad == 64 && !sw.starts("CATTUS_TOWER64", '0');
+    const bool resident64 = resident && cpad0 == 64, resident64_split = resident && cpad0 == 32 && p.w_frag && 1 + 2 * d.blocks <= (uint32_t)T64S_MAX_LAYERS;
+    // RESIDENT: the one-launch LDS-resident tower, a demand: what AUTO gives bf16 and f16x2 on these shapes, and for f16 -- only when asked
+    // for -- bf16's kernel on bf16's shapes with the per-layer f16 tower's bits; a SimpleTwoHeadedModel runs in f32 as under every form
+    if (cfg.tower_form == CATTUS_TOWER_RESIDENT && !simple) {
+        if (!((resident64 && (act == Act::BF16 || act == Act::F16)) || (resident64_split && act == Act::F16S)))
+            return fail(CATTUS_E_UNSUPPORTED, "tower_form RESIDENT needs dtype bf16, f16 or f16x2, value + policy head channels <= 32 and at most 64 filters (and no CATTUS_TOWER64=0)");
+        p.kind = act == Act::F16S ? TowerKind::Resident64Split : TowerKind::Resident64;
+        return CATTUS_OK;
+    }
     if (!tuned) p.kind = simple ? TowerKind::Simple : TowerKind::Generic;
     else if (cfg.tower_form == CATTUS_TOWER_WINOGRAD_F4) {
         p.kind = TowerKind::WinoF4;
@@ -1448,8 +1462,8 @@ int resolve_plan(const cattus_net_desc& d, const cattus_eval_config& cfg, const 
         p.kind = k4 ? TowerKind::Wino4 : TowerKind::Wino16;
         p.inplace = !sw.starts("CATTUS_WINO_INPLACE", '0');
         p.one_launch = k4 && p.inplace && !sw.starts("CATTUS_WINO_PERSIST", '0');
-    } else if (resident && act == Act::BF16 && cpad0 == 64) p.kind = TowerKind::Resident64;
-    else if (resident && act == Act::F16S && cpad0 == 32 && p.w_frag && 1 + 2 * d.blocks <= (uint32_t)T64S_MAX_LAYERS) p.kind = TowerKind::Resident64Split;
+    } else if (resident64 && act == Act::BF16) p.kind = TowerKind::Resident64;
+    else if (resident64_split && act == Act::F16S) p.kind = TowerKind::Resident64Split;
     else p.kind = TowerKind::PerLayer;
     return CATTUS_OK;
 }
@@ -1470,7 +1484,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
     memcpy(&cfg_copy, cfg_in, cfg_in->struct_size);
     cfg_copy.struct_size = sizeof(cattus_eval_config);
     const cattus_eval_config* cfg = &cfg_copy;
-    if (cfg->tower_form > CATTUS_TOWER_DIRECT_SPLITK) return fail(CATTUS_E_INVALID, "unknown tower_form %u", cfg->tower_form);
+    if (cfg->tower_form > CATTUS_TOWER_RESIDENT) return fail(CATTUS_E_INVALID, "unknown tower_form %u", cfg->tower_form);
     if (cfg->tail_leaves > cfg->max_batch) return fail(CATTUS_E_INVALID, "tail_leaves %u is more than max_batch %u", cfg->tail_leaves, cfg->max_batch);
     Switches sw;
     if (int src = sw.parse(switches)) return src;

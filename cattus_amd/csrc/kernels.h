@@ -210,19 +210,20 @@ void launch_trace_compare(const void* x, const TapSource& sx, const int* shifts,
 // waves on each of `cus` workgroups, iters x 4 MFMAs per wave; `out` holds cus * 256 floats.  Returns the launch's FLOPs.
 double launch_mfma_sustain(Act act, int cus, int iters, float* out, hipStream_t st);
 
-// ---- K1 resident: whole tower of a network with <= 64 (padded) filters in one launch, bf16 (see kernels.hip) ----
+// ---- K1 resident: whole tower of a network with <= 64 (padded) filters in one launch, bf16 or single-term f16 (see kernels.hip) ----
 struct Tower64Layer {
-    const void* w;      // [9][64][64] bf16 (stem: input channels padded to 64)
-    const float* bias;  // [64]
+    const void* w;      // [9][64][64] bf16 / f16 (stem: input channels padded to 64); f16: pre-scaled per output channel
+    const float* bias;  // [64]; f16: [64 biases | 64 inverse scales]
     int res;            // 1: add the block input (second conv of a residual block)
     int pad_;
 };
 struct Tower64Args {
     const uint64_t* planes;      // [n][C][w64] bitboards
     const Tower64Layer* layers;  // device array [nlayers]: stem, then (conv1, conv2) per block
-    void* out;                   // optional: [rows][64] bf16 tower output, rows = boards * tower_slots(S)
+    void* out;                   // bf16, optional: [rows][64] bf16 tower output, rows = boards * tower_slots(S); f16, required: the same in f32
+    unsigned* sat;               // f16: the evaluator's saturation counter (ConvOpts::saturated); bf16: not read
     uint32_t n, C, w64, S, nlayers;
-    // optional, fused K3: the two 1x1 head convs (+ folded BN + ReLU) on the resident tower output, written in the
+    // bf16 only, optional, fused K3: the two 1x1 head convs (+ folded BN + ReLU) on the resident tower output, written in the
     // layout the head FC kernels read (HeadsMfma::hv)
     const void* head_w;   // [32][64] bf16, value rows first, rows >= ocn zero
     const float* head_b;  // [32]: entries >= ocn are not used
@@ -231,8 +232,9 @@ struct Tower64Args {
 };
 // rows % 256 == 0; ch = 2: 128 rows per workgroup, ch = 4: one 64-slot board per workgroup (small batches; 128-slot
 // boards run as ch = 2).  layer_steps: with ch = 4 and boards of <= 63 pixels, one barrier per layer instead of three
-// (two layers of weights in LDS); same results.
-void launch_tower64(const Tower64Args& args, uint32_t rows, int ch, bool layer_steps, hipStream_t st,
+// (two layers of weights in LDS); same results.  act: Act::BF16, or Act::F16 with sat and out set and no head_w (the f32 head kernels read
+// out); anything else aborts.
+void launch_tower64(Act act, const Tower64Args& args, uint32_t rows, int ch, bool layer_steps, hipStream_t st,
                     hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 
 // ---- K1rs resident, split precision: the whole tower of a <= 64-filter f16x2 network in one launch (see kernels.hip) ----

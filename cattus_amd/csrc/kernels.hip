@@ -1375,12 +1375,16 @@ void launch_conv3x3_mfma(Act act, const void* in, const void* w, const float* bi
 // is its own output: nothing has to be handed to another workgroup, and nothing has to go through HBM.
 // The workgroup expands its boards' bitboard planes into LDS (the plane pack, fused), then runs stem +
 // 2 convs per residual block with the block input and the intermediate kept in two LDS buffers of
-// [rows][64 ch] bf16 (XOR-swizzled 128-byte rows, the conv kernel's layout), streaming only the weights:
+// [rows][64 ch] of T = bf16 or f16 (XOR-swizzled 128-byte rows, the conv kernel's layout), streaming only the weights:
 // waves 4-7 run the same LDS-DMA ring as in conv3x3_mfma_v2_kernel (3 slabs of [3 taps][64 cout][128 B]),
 // two steps ahead across layer boundaries; waves 0-3 are MFMA consumers.  One s_barrier per (layer, kernel
 // row) orders the ring and, at a layer boundary, one wave's LDS writes against its neighbours' reads.
 // Arithmetic per output element is that of the per-layer kernel, operation for operation (bf16 operands,
 // f32 accumulation in the same order, + bias, + skip, ReLU, one rounding to bf16), so results are bit-identical.
+// T = _Float16 (tower_form RESIDENT, never AUTO's choice) is conv3x3_mfma_v2_kernel<_Float16>'s tower in the same way: f16 operands
+// pre-scaled per output channel, fmaf(sum, inverse scale, bias), + skip, ReLU under the pixel mask, the clamp at 65504 counted in
+// Tower64Args::sat, one rounding to f16; the last layer leaves as plain f32 rows (CONV_OUT_F32) for the f32 head kernels, which follow
+// as launches of their own (fusing them into the tail, as tower64_split_kernel does, is the follow-up).
 //
 // CH = 2: 128 rows per workgroup, wave w owns row block w>>1 and the 32 couts of half w&1 (1x2 MFMA tiles).
 // CH = 4: 64 rows = one 64-slot board per workgroup (<= 256 boards), wave w owns the 32 pixels of half w>>1 and the
@@ -1396,13 +1400,17 @@ constexpr int R_LDS_W = 0;                    // 3 x 24 KiB
 // there is no room for zero rows: pixel slot 63, which such a board does not use, is kept zero and serves as one.
 constexpr int tower64_lds_bytes(int ch, bool ls) { return ls ? 6 * V2_SLAB + 2 * 64 * 128 : 3 * V2_SLAB + 2 * ((256 / ch) * 128 + 256); }
 
-template <int CH, bool BIG, bool LS = false>
+template <typename T, int CH, bool BIG, bool LS = false>
 __global__ void __launch_bounds__(512, 2) tower64_lds_kernel(Tower64Args A) {
     static_assert(NLOAD == 4, "512 threads: four consumer and four loader waves");
     static_assert(!LS || CH == 4, "layer steps: one board per workgroup only");
     constexpr int R_LDS_ACT = (LS ? 6 : 3) * V2_SLAB;
-    typedef __bf16 T;
-    typedef Mfma<T>::frag frag;
+    static_assert(sizeof(T) == 2, "128-byte rows of 64 channels");
+    // single-term f16 tower (conv3x3_mfma_v2_kernel<_Float16>'s layers): weights pre-scaled per output channel, L.bias = [64 biases | 64
+    // inverse scales], activations clamped at 65504 and counted in A.sat, the last layer as plain f32 rows to A.out, no fused heads
+    constexpr bool F16T = std::is_same<T, _Float16>::value;
+    typedef typename Mfma<T>::frag frag;
+    typedef T tx4 __attribute__((ext_vector_type(4)));
     constexpr int ROWS = 256 / CH;      // tower rows of this workgroup
     static_assert(CH == 2 || CH == 4, "128 or 64 rows per workgroup");
     constexpr int CB = 1;                // 32-cout blocks per consumer wave
@@ -1492,10 +1500,10 @@ __global__ void __launch_bounds__(512, 2) tower64_lds_kernel(Tower64Args A) {
             const int v = tid + it * 512;
             const int row = v >> 3, sl = v & 7;
             const uint32_t px = (uint32_t)(row0 + row) % SLOTS_PER_BOARD;
-            bf16x8 vals;
+            frag vals;
 #pragma unroll
             for (int i = 0; i < 8; i++) vals[i] = ((words[it][i] >> (px & 63)) & 1ull) ? (T)1.0f : (T)0.0f;
-            *reinterpret_cast<bf16x8*>(smem + R_LDS_ACT + ACT_BYTES + row * 128 + ((sl ^ ((row >> 1) & 7)) << 4)) = vals;
+            *reinterpret_cast<frag*>(smem + R_LDS_ACT + ACT_BYTES + row * 128 + ((sl ^ ((row >> 1) & 7)) << 4)) = vals;
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // written before this wave's first barrier
     }
@@ -1591,7 +1599,14 @@ __global__ void __launch_bounds__(512, 2) tower64_lds_kernel(Tower64Args A) {
         for (int cb = 0; cb < CB; cb++)
 #pragma unroll
             for (int g = 0; g < 4; g++) biasv[cb][g] = gbias[cb * 8 + g * 2];
-        if (layer == nlayers - 1 && A.head_w) {  // operands of the fused head convs: on their way under the last layer
+        f32x4 dsv[CB][4];  // f16: the inverse weight scales of the same couts
+        if constexpr (F16T) {
+#pragma unroll
+            for (int cb = 0; cb < CB; cb++)
+#pragma unroll
+                for (int g = 0; g < 4; g++) dsv[cb][g] = gbias[16 + cb * 8 + g * 2];
+        }
+        if (!F16T && layer == nlayers - 1 && A.head_w) {  // operands of the fused head convs: on their way under the last layer
             const T* hw_ = reinterpret_cast<const T*>(A.head_w);
 #pragma unroll
             for (int ks = 0; ks < 4; ks++) wa[ks] = *reinterpret_cast<const frag*>(hw_ + r * 64 + ks * 16 + h * 8);
@@ -1708,6 +1723,49 @@ __global__ void __launch_bounds__(512, 2) tower64_lds_kernel(Tower64Args A) {
                     const int slot16 = (coutb >> 3) + cb * 4 + g;  // 16-byte slot of couts coutb + cb*32 + g*8 .. +7
                     eoff[cb][pb][g] = obase + eaddr[pb] + ((slot16 ^ eswz[pb]) << 4);
                 }
+        if constexpr (F16T) {
+            // the per-layer f16 epilogue in its order: times the inverse scale plus bias (exact scale: a power of two), + skip, ReLU with
+            // the pixel mask, the clamp counted, one rounding to f16 -- the last layer instead as plain f32 rows for the f32 head kernels
+            const bool last = layer == nlayers - 1;
+            tx4 rv[CB][NPB][4];
+            if (L.res) {  // the block input lives in the buffer being overwritten: same addresses, all read first
+#pragma unroll
+                for (int cb = 0; cb < CB; cb++)
+#pragma unroll
+                    for (int pb = 0; pb < NPB; pb++)
+#pragma unroll
+                        for (int g = 0; g < 4; g++) rv[cb][pb][g] = *reinterpret_cast<const tx4*>(smem + eoff[cb][pb][g]);
+            }
+#pragma unroll
+            for (int cb = 0; cb < CB; cb++)
+#pragma unroll
+                for (int pb = 0; pb < NPB; pb++)
+#pragma unroll
+                    for (int g2 = 0; g2 < 2; g2++) {
+                        float y[8];
+#pragma unroll
+                        for (int j = 0; j < 8; j++) {
+                            const int g = g2 * 2 + (j >> 2), q = j & 3;
+                            float v = __builtin_fmaf(acc[cb][pb][g * 4 + q], dsv[cb][g][q], biasv[cb][g][q]);
+                            if (L.res) v = v + (float)rv[cb][pb][g][q];
+                            y[j] = pvalid[pb] && v > 0.0f ? v : 0.0f;
+                        }
+                        if (last) {
+                            float* of = reinterpret_cast<float*>(A.out) + ((size_t)row0 + rb * 64 + (pb0 + pb) * 32 + r) * 64 + coutb + cb * 32 + h * 4;
+                            *reinterpret_cast<f32x4*>(of + (g2 * 2) * 8) = *reinterpret_cast<f32x4*>(y);
+                            *reinterpret_cast<f32x4*>(of + (g2 * 2 + 1) * 8) = *reinterpret_cast<f32x4*>(y + 4);
+                            continue;
+                        }
+                        note_saturation(y, pvalid[pb], A.sat);
+#pragma unroll
+                        for (int gg = 0; gg < 2; gg++) {
+                            tx4 ov;
+#pragma unroll
+                            for (int q = 0; q < 4; q++) ov[q] = (T)(y[gg * 4 + q] < 65504.0f ? y[gg * 4 + q] : 65504.0f);
+                            *reinterpret_cast<tx4*>(smem + eoff[cb][pb][g2 * 2 + gg]) = ov;
+                        }
+                    }
+        } else {  // bf16 (not indented: the code as it was)
         // two code paths (uniform branch), packed f32 arithmetic: the MFMA pipes idle during an epilogue, so its
         // instruction count is what it costs
         typedef __attribute__((ext_vector_type(2))) float f32x2;
@@ -1761,10 +1819,12 @@ __global__ void __launch_bounds__(512, 2) tower64_lds_kernel(Tower64Args A) {
                             keep(finish(acc[cb][pb], g, biasv[cb][g], f32x2{0.0f, 0.0f}, f32x2{0.0f, 0.0f}), pb);
                     }
         }
+        }
         STAMP_ACC_END(5);
     }
     STAMP(2);
 
+    if constexpr (!F16T) {  // f16: the last layer's epilogue has stored the f32 rows; the f32 head kernels follow as launches of their own
     // ---- the two 1x1 head convs on the resident tower output (K3 fused; same MFMA order as head_conv_tile) ----
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // the loader waves have left: live waves only
     const int fin = (nlayers & 1) ? 0 : 1;  // the stem and every second conv of a block write buffer 0
@@ -1812,30 +1872,37 @@ __global__ void __launch_bounds__(512, 2) tower64_lds_kernel(Tower64Args A) {
             *reinterpret_cast<f32x4*>(out + ((size_t)row0 + row) * 64 + sl * 8) = v;
         }
     }
+    }
     STAMP(3);
     STAMP_FLUSH(wave);
 }
 
-// Every instance that exists, f(kernel, LDS bytes, CH, BIG, LS): one board per workgroup (CH = 4) on 64-slot boards only, one barrier
-// per layer (LS) with CH = 4 only.
-template <class F>
+// Every instance of element type T (__bf16, _Float16) that exists, f(kernel, LDS bytes, CH, BIG, LS): one board per workgroup (CH = 4) on
+// 64-slot boards only, one barrier per layer (LS) with CH = 4 only.
+template <typename T, class F>
 static void for_each_tower64(F&& f) {
     each_int<2, 4>([&](auto ch) { each_bool([&](auto big) { each_bool([&](auto ls) {
         constexpr int CH = decltype(ch)::value;
         constexpr bool BIG = decltype(big)::value, LS = decltype(ls)::value;
-        if constexpr (CH == 4 ? !BIG : !LS) f(&tower64_lds_kernel<CH, BIG, LS>, tower64_lds_bytes(CH, LS), ch, big, ls);
+        if constexpr (CH == 4 ? !BIG : !LS) f(&tower64_lds_kernel<T, CH, BIG, LS>, tower64_lds_bytes(CH, LS), ch, big, ls);
     }); }); });
 }
 
-void launch_tower64(const Tower64Args& args, uint32_t rows, int ch, bool layer_steps, hipStream_t st, hipEvent_t ev_start,
+void launch_tower64(Act act, const Tower64Args& args, uint32_t rows, int ch, bool layer_steps, hipStream_t st, hipEvent_t ev_start,
                     hipEvent_t ev_stop) {
+    if (act != Act::BF16 && !(act == Act::F16 && args.sat && args.out && !args.head_w)) {
+        fprintf(stderr, "cattus: launch_tower64: bf16, or f16 with Tower64Args::sat and ::out and no fused heads\n");
+        abort();
+    }
     const bool want_big = tower_slots(args.S) == 128;
     const int want_ch = ch == 4 && !want_big ? 4 : 2;
     const bool want_ls = want_ch == 4 && layer_steps && args.S * args.S <= 63;
-    for_each_tower64([&](auto kernel, int lds, auto c, auto big, auto ls) {
+    auto launch = [&](auto kernel, int lds, auto c, auto big, auto ls) {
         if (c == want_ch && big == want_big && ls == want_ls)
             hipExtLaunchKernelGGL(kernel, dim3(rows / (256 / c)), dim3(512), lds, st, ev_start, ev_stop, 0, args);
-    });
+    };
+    if (act == Act::F16) for_each_tower64<_Float16>(launch);
+    else for_each_tower64<__bf16>(launch);
 }
 
 // The opt-in for > 64 KiB of dynamic LDS is a per-device function attribute.  Every instance of every family gets it here, once
@@ -1848,7 +1915,8 @@ hipError_t prepare_device() {
     conv_opt_in<ConvV2<_Float16>>(err);
     conv_opt_in<ConvSplit>(err);
     conv_opt_in<ConvSplitW>(err);
-    for_each_tower64([&](auto kernel, int lds, auto...) { lds_opt_in(err, kernel, lds); });
+    for_each_tower64<__bf16>([&](auto kernel, int lds, auto...) { lds_opt_in(err, kernel, lds); });
+    for_each_tower64<_Float16>([&](auto kernel, int lds, auto...) { lds_opt_in(err, kernel, lds); });
     for (hipError_t e : {prepare_tower64_split(), prepare_wino(), prepare_wino4(), prepare_winof4(), prepare_wino4s(), prepare_wino_f16(), prepare_wino_f32(), prepare_splitk()})
         if (err == hipSuccess) err = e;
     return err;

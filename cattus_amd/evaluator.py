@@ -102,6 +102,8 @@ class EvalConfig(C.Structure):
 
 
 TOWER_FORMS = {"auto": 0, "direct": 1, "winograd": 2, "winograd_f4": 3, "direct_splitk": 4}  # cattus_tower_form
+# the one-launch LDS-resident tower as a demand (dtype f16: opt-in, the per-layer tower's bits; bf16 / f16x2: where "auto" already runs it)
+TOWER_FORMS_RESIDENT = {"resident": 5}
 # Diagnostic switches (include/cattus_hip_diag.h).  The library reads none of them from the environment; this binding -- the
 # harness of the tests and the timing scripts -- forwards the ones it finds there through cattus_hip_create_diag, so that
 # `CATTUS_TOWER64=0 python scripts/...` and monkeypatch.setenv keep working.  CATTUS_WINOGRAD=0/1 (rounds 3-4) maps to tower_form.
@@ -339,7 +341,9 @@ class HipEvaluator:
         cap, no stream shift, ``saturated`` stays 0; bits of its own (not the exact tower's); ``verify`` / ``trace`` hold it to the f32 shadow like any other.
         tower_form: "auto" | "direct" | "winograd" | "winograd_f4" | "direct_splitk" (cattus_tower_form; None = "auto", or what CATTUS_WINOGRAD=0/1 in the
         environment says; "winograd_f4", the F(4x4,3x3) form, and "direct_splitk", the direct form with the K walk divided over a workgroup's waves
-        for batches of a few leaves, are opt-in only: never what "auto" picks, and each has bits of its own).  switches: diagnostic switches for cattus_hip_create_diag (None = the CATTUS_* ones found in the
+        for batches of a few leaves, are opt-in only: never what "auto" picks, and each has bits of its own; "resident" (TOWER_FORMS_RESIDENT)
+        demands the one-launch LDS-resident tower of a network with at most 64 filters: for dtype "f16" opt-in, with the bits of "auto" and
+        one tower launch instead of 1 + 2 * blocks; for "bf16" / "f16x2" accepted where "auto" already runs it; refused everywhere else).  switches: diagnostic switches for cattus_hip_create_diag (None = the CATTUS_* ones found in the
         environment, {} = none).  calibration: sample positions, uint64 ``[n, C, plane_words]`` -- the f16 / f16x2 towers then
         take their stream shifts from the range measured on them instead of from the BatchNorm parameters
         (cattus_hip_create_calibrated; nothing to calibrate for f32 / bf16, which come out as without it, and nothing for "f32w"; "f16w", whose stream is f32, keeps the
@@ -364,7 +368,7 @@ class HipEvaluator:
         if switches is None:
             switches = {k: os.environ[k] for k in DIAG_SWITCHES if k in os.environ}
         self.tower_form = tower_form
-        cfg = EvalConfig(C.sizeof(EvalConfig), device, self.batch_size, self.plane_words, {**_DTYPES, **_DTYPES_WINO_F32}[dtype], flush_us, TOWER_FORMS[tower_form], int(tail_leaves))
+        cfg = EvalConfig(C.sizeof(EvalConfig), device, self.batch_size, self.plane_words, {**_DTYPES, **_DTYPES_WINO_F32}[dtype], flush_us, {**TOWER_FORMS, **TOWER_FORMS_RESIDENT}[tower_form], int(tail_leaves))
         h = C.c_void_p()
         buf = C.create_string_buffer(blob, len(blob))
         text = ";".join(f"{k}={v}" for k, v in switches.items()).encode() if switches else None

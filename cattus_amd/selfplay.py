@@ -599,11 +599,12 @@ def write_summary(path, summary: dict):
 
 def tower_form_from_inference(inf: dict) -> str:
     """model.inference.tower_form of the engine JSON: one of the evaluator's TOWER_FORMS names, "auto" when absent."""
-    from .evaluator import TOWER_FORMS
+    from .evaluator import TOWER_FORMS, TOWER_FORMS_RESIDENT
 
+    forms = {**TOWER_FORMS, **TOWER_FORMS_RESIDENT}
     form = inf.get("tower_form", "auto")
-    if form not in TOWER_FORMS:
-        raise SystemExit(f"model.inference.tower_form is one of {sorted(TOWER_FORMS)}, got {form!r}")
+    if form not in forms:
+        raise SystemExit(f"model.inference.tower_form is one of {sorted(forms)}, got {form!r}")
     return form
 
 
@@ -638,7 +639,8 @@ def main(argv=None):
     # absent or 0: off
     tail_leaves = int(inf.get("tail_leaves", 0))
     # optional: the form of the f16x2 tower (cattus_tower_form): "auto" (absent), "direct", "winograd", "winograd_f4", or "direct_splitk" -- the
-    # direct form for batches of a few leaves, the reference's threads: 8, batch_size: 1 (include/cattus_hip.h)
+    # direct form for batches of a few leaves, the reference's threads: 8, batch_size: 1 (include/cattus_hip.h); or "resident": the one-launch
+    # LDS-resident tower of a network with at most 64 filters, for dtype f16 the only way to it
     tower_form = tower_form_from_inference(inf)
 
     def load(path):

@@ -57,7 +57,7 @@ typedef enum cattus_dtype {
      * Coverage: the Winograd form's -- an 8x8 board, at least one residual block, a multiple of 64 filters >= 128, vhc + phc <= 32;
      * anything else returns CATTUS_E_UNSUPPORTED, never other bits under this name.  Activations are capped at 16,376 (a transformed
      * input is a signed sum of four and must stay inside the f16 range) and counted in cattus_stats.saturated.
-     * tower_form: AUTO and WINOGRAD both mean this form; DIRECT, WINOGRAD_F4 and DIRECT_SPLITK are refused with CATTUS_E_UNSUPPORTED.
+     * tower_form: AUTO and WINOGRAD both mean this form; DIRECT, WINOGRAD_F4, DIRECT_SPLITK and RESIDENT are refused with CATTUS_E_UNSUPPORTED.
      * tail_leaves is ignored (cattus_hip_tail_leaves reports 0).  A SimpleTwoHeadedModel blob runs in f32, as under every dtype.
      * cattus_hip_create_calibrated: the stream is f32, so a measured lift buys nothing here; the tower keeps the shifts of the BatchNorm
      * estimate and takes from the sample only the headroom guard (a channel's shift is lowered while its measured largest |value| 2^t
@@ -81,7 +81,7 @@ typedef enum cattus_dtype {
      * (csrc/wino_f32_rule.h, tests/wino_f32_layer_ref.cpp).  cattus_hip_verify / _trace hold it to the f32 shadow like any other dtype.
      * Coverage: CATTUS_DTYPE_F16W's -- an 8x8 board, at least one residual block, a multiple of 64 filters >= 128, vhc + phc <= 32;
      * anything else returns CATTUS_E_UNSUPPORTED, never other bits under this name.  tower_form: AUTO and WINOGRAD both mean this form;
-     * DIRECT, WINOGRAD_F4 and DIRECT_SPLITK are refused with CATTUS_E_UNSUPPORTED.  tail_leaves is ignored (cattus_hip_tail_leaves reports
+     * DIRECT, WINOGRAD_F4, DIRECT_SPLITK and RESIDENT are refused with CATTUS_E_UNSUPPORTED.  tail_leaves is ignored (cattus_hip_tail_leaves reports
      * 0).  A SimpleTwoHeadedModel blob runs in f32, as under every dtype.  cattus_hip_create_calibrated has nothing to calibrate: it
      * validates planes and n and is then cattus_hip_create.  cattus_hip_stream_range stays CATTUS_E_UNSUPPORTED (it measures on the exact
      * per-layer tower only).
@@ -139,6 +139,29 @@ typedef enum cattus_tower_form {
      * (9-12 leaves per batch, Python threads around cattus_hip_apply): 17.3-19.2 k -> 21.1-27.0 k leaves/s on chess 20x256.  Not measured:
      * in-kernel stamps or counters of the new kernel, filter counts other than 128 and 256, two evaluators sharing a device. */
     CATTUS_TOWER_DIRECT_SPLITK = 4,
+    /* The whole conv tower in ONE launch with the activations resident in LDS, for networks of at most 64 (padded) filters -- every
+     * network the reference trains.  A demand, like WINOGRAD: CATTUS_E_UNSUPPORTED where no such kernel covers the evaluator.
+     *   dtype f16: opt-in, NEVER chosen by AUTO (which runs 1 + 2 * blocks conv3x3_mfma_v2_kernel launches).  tower64_lds_kernel in its
+     *     f16 instantiation, on the shapes dtype bf16 runs that kernel on: value + policy head channels <= 32 and at most 64 filters.  THE
+     *     BITS DO NOT CHANGE: every logit and value equals, bit for bit, what the same blob returns from dtype f16 with AUTO, for every n,
+     *     through every entry point, and cattus_stats.saturated counts the same elements (tests/test_resident_f16_gpu.py).  The last layer
+     *     leaves the launch as f32 rows and the two f32 head launches follow: three launches per step where bf16 has two.
+     *   dtype bf16, f16x2: accepted exactly where AUTO already runs tower64_lds_kernel / tower64_split_kernel, with that plan and its bits.
+     *   dtype f32, f16w, f32w, more than 64 filters, CATTUS_TOWER64=0: CATTUS_E_UNSUPPORTED.  A SimpleTwoHeadedModel blob runs in f32 as
+     *     under every form.  tail_leaves is ignored.
+     * MEASURED on one MI355X (scripts/resident_f16_time.py -> profiles/resident_f16.txt: one process, max_batch = n, four evaluators
+     * alternating over three rounds, 300 steps through cattus_hip_eval_device, min; f16 RESIDENT | f16 AUTO | bf16 | f16x2, ms per step):
+     *   hex7 6x64:  32 leaves 0.040 | 0.072 | 0.024 | 0.053,  128: 0.041 | 0.075 | 0.025 | 0.053,  512: 0.057 | 0.104 | 0.038 | 0.090
+     *     (the tower: one launch of 24.6 / 26.0 / 42.4 us against 13 of 4.7 / 4.7 / 6.3 us);
+     *   chess 7x16: 64 leaves 0.049 | 0.083 | 0.031 | 0.061,  256: 0.052 | 0.091 | 0.032 | 0.062  (one launch of 30.6 / 32.8 us against 15 of 4.7 / 4.9).
+     * Against the 12 % by which two boxes differ on one binary: RECOMMENDED FOR dtype f16 ON ALL FIVE SHAPES (41-45 % less time per step,
+     * 1.7-1.8x); no shape was measured on which it is not.  It is also 16-36 % faster per step than f16x2 there, and takes 1.5-1.7x bf16's
+     * time: the f16 epilogue, and the f32 head convs as a third launch (fusing them into the tower's tail is the follow-up).  The estimate
+     * it was built on (~0.04 against ~0.11 ms at 128 leaves, 2.5x; 1.5x at 512) held for the resident step (0.041) and
+     * MISSED THE RATIO at 128 leaves, where f16 AUTO is faster than estimated (0.075: its launches take 4.7 us, not bf16's 6.3 of round 1),
+     * and was exceeded at 512 (1.8x).  Not measured: in-kernel stamps or counters of the f16 instantiations, filter counts other than 64
+     * and 16 (padded to 64), two evaluators sharing a device. */
+    CATTUS_TOWER_RESIDENT = 5,
 } cattus_tower_form;
 
 /* Replaces the reference's InferenceConfig + batch_size (engine/src/net/model.rs:17-25,
@@ -152,7 +175,7 @@ typedef struct cattus_eval_config {
     uint32_t plane_words; /* u64 words per bitboard plane: chess 1, ttt 1, hex 2 (u128 as lo,hi) */
     uint32_t dtype;       /* cattus_dtype */
     uint32_t flush_us;    /* partial-batch deadline of the leaf server (reference: 20 ms, net/mod.rs:96) */
-    uint32_t tower_form;  /* cattus_tower_form; ignored by every dtype but f16x2 */
+    uint32_t tower_form;  /* cattus_tower_form; the forms 1 to 4 are ignored by every dtype but f16x2 */
     /* Short batches of the Winograd F(2x2,3x3) tower (f16x2, AUTO with max_batch > 128 or WINOGRAD).  0, the default: nothing changes.
      * k > 0: a batch of n <= k leaves runs the layers behind the stem on conv3x3_wino4s_kernel, a kernel for the same arithmetic whose
      * workgroup takes 2 boards x 32 output channels where the tower's takes 4 x 64 -- four times as many workgroups for a batch that

@@ -37,6 +37,8 @@ struct CattusEvalConfig {
     /// 3 = Winograd F(4x4,3x3) (opt-in, never what auto picks; activations capped at 655: see include/cattus_hip.h)
     /// 4 = direct with the K walk split over a workgroup's waves (opt-in, never what auto picks; bits of its own): for evaluators whose
     /// batches hold a few leaves -- threads: 8, batch_size: 1 through the leaf server; slower than direct from 64 leaves on
+    /// 5 = the whole tower in one LDS-resident launch, networks of at most 64 filters (dtype f16: opt-in, the bits of auto; bf16 / f16x2:
+    /// where auto already runs it); refused where no such kernel covers the evaluator
     tower_form: u32,
     /// batches of at most this many leaves of the Winograd F(2x2,3x3) tower run on its small-tile kernel: the same bits, more workgroups
     /// for a short batch; 0 = off; ignored on every other plan (uint32_t tail_leaves of include/cattus_hip.h)
