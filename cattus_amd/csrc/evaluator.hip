@@ -348,6 +348,10 @@ enum class TowerKind {
     // over the waves of a workgroup (kernels_splitk.hip), for batches of a few leaves: only for tower_form DIRECT_SPLITK, never by AUTO; its
     // f32 summation order, and so its bits, are its own; rows in the direct form's layout
     DirectSplitK,
+    // dtype f16r (Act::F16 with this kind, and no other kind for that dtype): the per-layer direct f16 tower with the residual stream kept
+    // in f32 (K1hr: conv3x3_f16r_kernel for the stem and every conv2, dtype f16's own layer for every conv1; f16r_rule.h has the buffer
+    // plan): dtype f16's weights, scales, shifts and coverage, bits of its own from point 2 on, always one launch per layer
+    PerLayerStream,
 };
 struct TowerPlan {
     TowerKind kind = TowerKind::Generic;
@@ -587,8 +591,9 @@ int build(cattus_eval* e, const float* p, const Calibration* cal) {
     if (act_f16_family(e->act) && e->stream_shift_on) {
         // (the F(4x4) form's cap is 25x tighter: its headroom is a quarter of that cap, as the default is of the F(2x2) form's)
         const double headroom = plan.kind == TowerKind::WinoF4 ? WINOF4_CAL_HEADROOM : STREAM_CAL_HEADROOM;
-        // (the f16w tower's stream is f32: calibrated, it keeps the estimate's shifts and takes the measured guard alone -- weight_layout.h)
-        if (cal && plan.kind == TowerKind::WinoF16)
+        // (the f16w tower's stream is f32: calibrated, it keeps the estimate's shifts and takes the measured guard alone -- weight_layout.h;
+        // so does the f16r tower, whose stream is f32 as well: its shifts serve the f16 operand copy, and a seeded net keeps its shifts and bits)
+        if (cal && (plan.kind == TowerKind::WinoF16 || plan.kind == TowerKind::PerLayerStream))
             e->stream_shifts = calibrated_stream_shifts_f32_stream(choose_stream_shift(d, p, &e->stream_shift, STREAM_NO_CEILING), cal->abs_max, headroom);
         else if (cal) e->stream_shifts = calibrated_stream_shifts(cal->s2, cal->abs_max, headroom), e->stream_shift = stream_shift_global(cal->s2);
         else e->stream_shifts = choose_stream_shift(d, p, &e->stream_shift, plan.kind == TowerKind::WinoF4 ? WINOF4_STREAM_CEILING : STREAM_NO_CEILING);
@@ -771,6 +776,7 @@ struct Forward {
         TapSource s{};
         s.C = F, s.hw = e->hw, s.slots = e->slots, s.pitch = FP;
         if (!e->plan.tuned()) s.layout = TAP_NCHW_F32;
+        else if (e->plan.kind == TowerKind::PerLayerStream) return f16r_tap_source(l, F, e->hw, e->slots, FP);
         else if (e->plan.wino()) s.layout = TAP_ROWS_WINO_F32;
         else if (e->act == Act::F32 || (act_f16_family(e->act) && l == 2 * d.blocks)) s.layout = TAP_ROWS_F32;
         else s.layout = e->act == Act::BF16 ? TAP_ROWS_BF16 : e->act == Act::F16 ? TAP_ROWS_F16 : TAP_ROWS_F16X2;
@@ -898,6 +904,32 @@ struct Forward {
         return a;
     }
 
+    // dtype f16r: layer l of f16r_rule.h's plan -- the stem and every conv2 on the stream kernel (S in f32, updated in place, and its f16
+    // operand copy A), every conv1 on dtype f16's layer (A -> M); the buffers' roles never move, so a layer is a function of l alone
+    const void* per_layer_stream_step(uint32_t l) {
+        void* const buf[4] = {L.a.p, L.t.p, L.y.p, L.x0.p};  // F16R_BUF_A, _T, _Y, _X0
+        const F16rLayer fl = f16r_layer(l, d.blocks);
+        const ConvLayer& c = l == 0 ? e->stem : (l & 1) ? *e->c1[(l - 1) / 2] : *e->c2[(l - 1) / 2];
+        if (!f16r_stream_layer(l)) {
+            conv_mfma(c, buf[fl.reads], nullptr, buf[fl.writes], 0);
+            return buf[fl.writes];
+        }
+        const bool stem = l == 0, fused_stem = stem && stem_is_fused(d.planes, e->pack_separately);
+        const StemInput stem_in{d_planes, n, d.planes, w64};
+        if (stem && !fused_stem) launch_pack_planes_nhwc(e->act, d_planes, n, nb, d.planes, w64, S, e->cpad0, L.x0.p, st);
+        hipEvent_t s0 = ev(), s1 = ev();
+        launch_conv3x3_f16r(buf[fl.reads], c.w.p, c.b.as<float>(), static_cast<float*>(buf[fl.writes]), fl.adds != F16R_NONE,
+                            fl.writes_copy == F16R_NONE ? nullptr : buf[fl.writes_copy], nb, stem ? e->cpad0 : FP, FP, S, st, s0, s1,
+                            fused_stem ? &stem_in : nullptr, f16r_is_last(l, d.blocks), e->conv_opts);
+        return buf[fl.writes];
+    }
+
+    const void* per_layer_stream() {
+        for (uint32_t l = 0; l < f16r_layers(d.blocks); l++) seen(l, per_layer_stream_step(l), tower_source(l));
+        void* const buf[3] = {L.a.p, L.t.p, L.y.p};
+        return buf[f16r_head_input()];
+    }
+
     // Wino16 / Wino4 / WinoF4 / WinoF16 / WinoF32: the stem on the direct kernel (the split one, the f16 one under dtype f16w, the f32 one under f32w),
     // every layer behind it in Winograd form, f32 rows between the layers
     int wino() {
@@ -976,6 +1008,7 @@ int enqueue_forward(cattus_eval* e, Lane& L, const uint64_t* d_planes, uint32_t 
         case TowerKind::Simple: f.simple(); break;
         case TowerKind::Generic: f.heads_generic(f.generic()); break;
         case TowerKind::PerLayer: f.heads_mfma(f.per_layer()); break;
+        case TowerKind::PerLayerStream: f.heads_mfma(f.per_layer_stream()); break;
         case TowerKind::DirectSplitK: f.heads_mfma(f.per_layer()); break;  // the stem through conv_mfma, every layer behind it through conv_splitk
         case TowerKind::Resident64: f.heads_mfma(f.resident64()); break;
         case TowerKind::Resident64Split: f.heads_mfma(f.resident64_split()); break;
@@ -1305,6 +1338,7 @@ CATTUS_API const char* cattus_hip_tower_kernel(const cattus_eval* e) {
         case TowerKind::WinoF16: return "conv3x3_wino_f16_kernel";
         case TowerKind::WinoF32: return "conv3x3_wino_f32_kernel";
         case TowerKind::DirectSplitK: return "conv3x3_splitk_kernel";
+        case TowerKind::PerLayerStream: return "conv3x3_f16r_kernel";
         case TowerKind::PerLayer: break;
     }
     return e->act != Act::F16S ? "conv3x3_mfma_v2_kernel" : e->plan.w_frag ? "conv3x3_splitw_kernel" : "conv3x3_split_kernel";
@@ -1344,7 +1378,7 @@ CATTUS_API int cattus_hip_stem_input(const cattus_eval* e, uint32_t* channels, u
     if (!e) return fail(CATTUS_E_INVALID, "NULL argument");
     if (channels) *channels = e->cpad0;
     // the towers that go through Forward::conv_mfma; the resident ones expand the planes in their one launch
-    if (packed) *packed = (e->plan.kind == TowerKind::PerLayer || e->plan.kind == TowerKind::DirectSplitK || e->plan.wino()) && !stem_is_fused(e->d.planes, e->pack_separately);
+    if (packed) *packed = (e->plan.kind == TowerKind::PerLayer || e->plan.kind == TowerKind::PerLayerStream || e->plan.kind == TowerKind::DirectSplitK || e->plan.wino()) && !stem_is_fused(e->d.planes, e->pack_separately);
     return CATTUS_OK;
 }
 
@@ -1419,6 +1453,16 @@ int resolve_plan(const cattus_net_desc& d, const cattus_eval_config& cfg, const 
         *plan = TowerPlan();
         plan->kind = TowerKind::WinoF32;
         plan->inplace = !sw.starts("CATTUS_WINO_INPLACE", '0');
+        return CATTUS_OK;
+    }
+    // dtype f16r: the per-layer direct f16 tower with an f32 residual stream and nothing else -- every shape dtype f16 runs on the MFMA
+    // per-layer tower (wider heads were refused above: the generic path is f32); AUTO means it, the forms 1-4 are ignored (they name forms of the
+    // f16x2 tower; dtype f16 ignores DIRECT alike), RESIDENT is refused (no resident kernel keeps an f32 stream yet: the follow-up), tail_leaves is ignored
+    if (cfg.dtype == CATTUS_DTYPE_F16R && !simple) {
+        if (cfg.tower_form == CATTUS_TOWER_RESIDENT)
+            return fail(CATTUS_E_UNSUPPORTED, "dtype f16r has no LDS-resident form: no resident kernel keeps an f32 residual stream (tower_form AUTO)");
+        *plan = TowerPlan();
+        plan->kind = TowerKind::PerLayerStream;
         return CATTUS_OK;
     }
     // the 4-frequency kernel wherever it covers the layer shape (filters a multiple of 64), else the 16-frequency one (128)
@@ -1503,7 +1547,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
         return fail(CATTUS_E_INVALID, "plane_words %u cannot hold a %ux%u board", cfg->plane_words, d.board, d.board);
     if (d.planes * cfg->plane_words > 128) return fail(CATTUS_E_UNSUPPORTED, "more than 128 plane words per leaf");
     if (cfg->dtype != CATTUS_DTYPE_F32 && cfg->dtype != CATTUS_DTYPE_BF16 && cfg->dtype != CATTUS_DTYPE_F16X2 && cfg->dtype != CATTUS_DTYPE_F16 &&
-        cfg->dtype != CATTUS_DTYPE_F16W && cfg->dtype != CATTUS_DTYPE_F32W)
+        cfg->dtype != CATTUS_DTYPE_F16W && cfg->dtype != CATTUS_DTYPE_F32W && cfg->dtype != CATTUS_DTYPE_F16R)
         return fail(CATTUS_E_INVALID, "unknown dtype %u", cfg->dtype);
     if (!simple && (size_t)d.phc * d.board * d.board * 8 * 4 > 64 * 1024) return fail(CATTUS_E_UNSUPPORTED, "policy head too wide for the FC kernel");
 
@@ -1556,7 +1600,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
     e->act = simple ? Act::F32
              : cfg->dtype == CATTUS_DTYPE_BF16 ? Act::BF16
              : cfg->dtype == CATTUS_DTYPE_F16X2 ? Act::F16S
-             : cfg->dtype == CATTUS_DTYPE_F16 || cfg->dtype == CATTUS_DTYPE_F16W ? Act::F16  // f16w: the direct f16 stem; resolve_plan chooses its tower
+             : cfg->dtype == CATTUS_DTYPE_F16 || cfg->dtype == CATTUS_DTYPE_F16W || cfg->dtype == CATTUS_DTYPE_F16R ? Act::F16  // f16w: the direct f16 stem, f16r: f16 operands; resolve_plan chooses their towers
                                               : Act::F32;  // f32w too: the direct f32 stem and f32 rows; resolve_plan chooses its tower
     // the tuned towers' layout: whole workgroups of boards, filters in whole 64-channel groups (zero channels), the planes in whole
     // 128-byte rows; the other towers pad nothing
@@ -1672,7 +1716,7 @@ int create_calibrated_impl(const void* weights, size_t nbytes, const cattus_eval
     uint32_t filters = 0;  // 0: SimpleTwoHeadedModel (or no blob at all, which create_impl refuses)
     if (nbytes >= HEADER_BYTES) memcpy(&filters, (const char*)weights + 8 + 5 * 4, 4);
     // only the f16 towers shift their stream: everything else is cattus_hip_create
-    if ((cfg->dtype != CATTUS_DTYPE_F16X2 && cfg->dtype != CATTUS_DTYPE_F16 && cfg->dtype != CATTUS_DTYPE_F16W) || filters == 0) return create_impl(weights, nbytes, cfg, switches, out);
+    if ((cfg->dtype != CATTUS_DTYPE_F16X2 && cfg->dtype != CATTUS_DTYPE_F16 && cfg->dtype != CATTUS_DTYPE_F16W && cfg->dtype != CATTUS_DTYPE_F16R) || filters == 0) return create_impl(weights, nbytes, cfg, switches, out);
     cattus_eval_config mcfg{};
     mcfg.struct_size = sizeof mcfg, mcfg.device = cfg->device, mcfg.max_batch = std::min(n, 256u), mcfg.plane_words = cfg->plane_words;
     mcfg.dtype = CATTUS_DTYPE_F32, mcfg.flush_us = cfg->flush_us, mcfg.tower_form = CATTUS_TOWER_AUTO;

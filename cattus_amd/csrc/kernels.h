@@ -10,6 +10,7 @@
 #include "tap_layout.h"   // TapSource, TraceRecord: where a point's activations live, the rule of a trace record
 #include "winof4_rule.h"  // the Winograd F(4x4, 3x3) form: matrices, transforms, geometry, cap, U index
 #include "splitk_rule.h"  // the split-K direct form: ways, ranges, reduction order, grid map, LDS plan
+#include "f16r_rule.h"    // dtype f16r: the epilogue with an f32 residual stream, the lane buffers' roles, the tap layout per point
 
 namespace cattus {
 
@@ -87,6 +88,17 @@ void launch_conv3x3_mfma(Act act, const void* in, const void* w, const float* bi
                          uint32_t bpad, uint32_t cin, uint32_t cout, uint32_t S, hipStream_t st,
                          hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, const StemInput* stem = nullptr,
                          int flags = 0, const ConvOpts& opts = ConvOpts());
+
+// ---- K1hr: the single-term f16 layer with the residual stream in f32 (dtype f16r; conv3x3_f16r_kernel in kernels.hip; f16r_rule.h has
+// the epilogue, the buffer plan and the tap layouts) ----
+// The Act::F16 layer of launch_conv3x3_mfma -- in, w, bias = [cout biases | cout inverse scales], the tiles, ConvOpts -- except for what
+// leaves it: `stream` [bpad][slots][cout] plain f32 rows, not clamped, is the layer's output and, with `skip`, also its skip rows, updated
+// in place (the lane that reads an element writes it; `in` must be another buffer); `copy` [bpad][slots][cout] f16 rows receives
+// f16(min(y, 65504)), counted in ConvOpts::saturated beyond it, unless `last` (the tower's last layer writes the stream alone; copy may be
+// NULL then).  stem as there; a stem layer has no skip.  Same MFMA sequence per accumulator as the Act::F16 layer.
+void launch_conv3x3_f16r(const void* in, const void* w, const float* bias, float* stream, bool skip, void* copy, uint32_t bpad, uint32_t cin,
+                         uint32_t cout, uint32_t S, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, const StemInput* stem, bool last,
+                         const ConvOpts& opts);
 
 // ---- K1w: the split-precision conv in Winograd F(2x2, 3x3) form (kernels_wino.hip) ----
 // 8x8 boards only; in / res / out are PLAIN F32 rows [row][channel] (what CONV_OUT_F32 writes: a tower in this form keeps f32

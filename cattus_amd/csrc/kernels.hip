@@ -4,6 +4,7 @@
 //                                                       network of <= 32 planes are expanded straight into LDS by K1 / K1s / K1r
 //                                                       instead, more planes are packed in the tower's own layout (all four)
 //   K1  conv3x3_mfma_v2<T, HAS_RES, BIG, STEM>          3x3 conv + folded BN (+skip) + ReLU, one launch per layer (MFMA-bound), bf16 / f32
+//   K1hr conv3x3_f16r<HAS_RES, BIG, STEM, CB, PBW>      the same body on f16 operands with the residual stream in f32 (dtype f16r, f16r_rule.h)
 //   K1s conv3x3_splitw<HAS_RES, BIG, STEM, CB>          the same layer of the split-precision tower (dtype f16x2, the default):
 //                                                       operands as pairs of f16 values, three f16 MFMA terms per product;
 //                                                       weights from L2 into a register ring, activations through LDS
@@ -342,12 +343,18 @@ __device__ __forceinline__ void stage_tile(const f32x16 (&acc)[CB][PBW], char* s
 //     k order per output element, so the result does not depend on which of the two ran.
 // PBW: 32-pixel blocks per consumer wave.  2: the workgroup covers 256 tower rows; 1 (with CB = 1): 128 rows, 32 pixels per
 //     wave -- twice the workgroups and half the MFMA chain per wave, for grids that would otherwise leave CUs empty.
-template <typename T, bool HAS_RES, bool BIG, bool STEM = false, int CB = 2, int PBW = 2>
-__global__ void __launch_bounds__(256 + 64 * NLOAD, (4 + NLOAD) / 4)
-    conv3x3_mfma_v2_kernel(const T* __restrict__ in, const T* __restrict__ w, const float* __restrict__ bias,
-                           const T* __restrict__ res, T* __restrict__ out, unsigned* __restrict__ sat, int cin, int cout, int S,
-                           int flags, StemPlanes<STEM> sp) {
+// STREAM (T = _Float16 only; K1hr, dtype f16r, f16r_rule.h): the residual stream lives in `stream` as plain f32 rows [row][cout], not
+//     clamped -- the skip rows (HAS_RES) are read from it and the layer's output is written back to it, in place: the lane that reads
+//     a skip element is the lane that writes it, and `in` is another buffer, so no neighbour reads `stream`; `res` is not read.
+//     `out` receives the operand copy f16(min(y, 65504)), counted in `sat` beyond it, unless flags & CONV_OUT_F32 (the tower's last
+//     layer: the stream alone).  Roles, LDS plan, loaders, ring and main loop are the f16 layer's, MFMA for MFMA.
+// The body of the two __global__ functions below.  (No __restrict__ here: the kernels' own arguments carry it, and the inlined body then
+// compiles to what it compiled to as a kernel -- the existing instances keep their assembly.)
+template <typename T, bool HAS_RES, bool BIG, bool STEM, int CB, int PBW, bool STREAM>
+__device__ __forceinline__ void conv3x3_mfma_v2_layer(const T* in, const T* w, const float* bias, const T* res, T* out, float* stream, unsigned* sat,
+                                                      int cin, int cout, int S, int flags, StemPlanes<STEM> sp) {
     static_assert(NLOAD == 4, "the stem expansion, the 32-cout tile and the piece counts below assume four loader waves");
+    static_assert(!STREAM || std::is_same<T, _Float16>::value, "the f32 residual stream belongs to the single-term f16 tower");
     // single-term f16 tower: weights pre-scaled per output channel (`bias` = [cout biases | cout inverse scales]), activations
     // clamped at 65504 and counted in `sat`, flags & CONV_OUT_F32 = plain f32 output rows; `sat` / `flags` are not read otherwise
     constexpr bool F16T = std::is_same<T, _Float16>::value;
@@ -510,13 +517,19 @@ __global__ void __launch_bounds__(256 + 64 * NLOAD, (4 + NLOAD) / 4)
             ds8[q] = *reinterpret_cast<const f32x4*>(bias + cout + cout0 + cg * 8 + q * 4);
         }
     }
-    constexpr bool RES_EARLY = HAS_RES && sizeof(T) == 2;
-    T resv[EIT][8];
+    constexpr bool RES_EARLY = HAS_RES && sizeof(T) == 2;  // STREAM: f32 skip rows, twice the registers -- every instance still fits
+    typedef typename std::conditional<STREAM, float, T>::type SkipT;
+    SkipT resv[EIT][8];
     if (RES_EARLY) {
 #pragma unroll
         for (int i = 0; i < EIT; i++) {
             const size_t off = ((size_t)row0 + wave * PXW + i * RPT + prow) * (size_t)cout + cout0 + cg * 8;
-            *reinterpret_cast<f32x4*>(resv[i]) = *reinterpret_cast<const f32x4*>(res + off);
+            if constexpr (STREAM) {
+                reinterpret_cast<f32x4*>(resv[i])[0] = reinterpret_cast<const f32x4*>(stream + off)[0];
+                reinterpret_cast<f32x4*>(resv[i])[1] = reinterpret_cast<const f32x4*>(stream + off)[1];
+            } else {
+                *reinterpret_cast<f32x4*>(resv[i]) = *reinterpret_cast<const f32x4*>(res + off);
+            }
         }
     }
 
@@ -610,6 +623,29 @@ __global__ void __launch_bounds__(256 + 64 * NLOAD, (4 + NLOAD) / 4)
             float v[8];
             staged_read(v, smem + stage_row<CB>(tile0, 32768, px), px, cg);
             const size_t off = (wrow0 + px) * (size_t)cout + cout0 + cg * 8;
+            if constexpr (STREAM) {  // K1hr: f16r_rule.h's epilogue per element; the stream row in f32, then its f16 operand copy
+                float y[8];
+                T cv[8];
+                unsigned nsat = 0;
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    const F16rOut o = f16r_finish(v[j], ds8[j >> 2][j & 3], bias8[j >> 2][j & 3], HAS_RES ? (float)resv[i][j] : 0.0f, HAS_RES, pslot0 + px < S * S);
+                    y[j] = o.stream, cv[j] = o.copy, nsat += o.counted ? 1u : 0u;
+                }
+                float* sf = stream + off;
+                const bool last = (flags & CONV_OUT_F32) != 0;  // the tower's last layer: the stream alone, for the f32 head kernels
+                if (!last && nsat) atomicAdd(sat, nsat);          // note_saturation's rule: one atomic add on the clamp path only
+                if constexpr (CB == 1) {  // plain / non-temporal stores as below
+                    reinterpret_cast<f32x4*>(sf)[0] = *reinterpret_cast<f32x4*>(y);
+                    reinterpret_cast<f32x4*>(sf)[1] = *reinterpret_cast<f32x4*>(y + 4);
+                    if (!last) *reinterpret_cast<f32x4*>(out + off) = *reinterpret_cast<f32x4*>(cv);
+                } else {
+                    __builtin_nontemporal_store(*reinterpret_cast<f32x4*>(y), reinterpret_cast<f32x4*>(sf));
+                    __builtin_nontemporal_store(*reinterpret_cast<f32x4*>(y + 4), reinterpret_cast<f32x4*>(sf) + 1);
+                    if (!last) __builtin_nontemporal_store(*reinterpret_cast<f32x4*>(cv), reinterpret_cast<f32x4*>(out + off));
+                }
+                continue;
+            }
             if constexpr (F16T) {  // the accumulator carries the weights' power-of-two scale: times its inverse is exact
 #pragma unroll
                 for (int j = 0; j < 8; j++) v[j] = __builtin_fmaf(v[j], ds8[j >> 2][j & 3], bias8[j >> 2][j & 3]);
@@ -669,6 +705,23 @@ __global__ void __launch_bounds__(256 + 64 * NLOAD, (4 + NLOAD) / 4)
     STAMP(3);
     STAMP_RT(6);
     STAMP_FLUSH(wave);
+}
+
+template <typename T, bool HAS_RES, bool BIG, bool STEM = false, int CB = 2, int PBW = 2>
+__global__ void __launch_bounds__(256 + 64 * NLOAD, (4 + NLOAD) / 4)
+    conv3x3_mfma_v2_kernel(const T* __restrict__ in, const T* __restrict__ w, const float* __restrict__ bias,
+                           const T* __restrict__ res, T* __restrict__ out, unsigned* __restrict__ sat, int cin, int cout, int S,
+                           int flags, StemPlanes<STEM> sp) {
+    conv3x3_mfma_v2_layer<T, HAS_RES, BIG, STEM, CB, PBW, false>(in, w, bias, res, out, nullptr, sat, cin, cout, S, flags, sp);
+}
+
+// K1hr (dtype f16r): the f16 layer above with the residual stream in f32.  `stream` is skip rows and output at once and carries no
+// __restrict__; HAS_RES = false is the stem (STEM: from the planes; else the packed stem), which only writes it.
+template <bool HAS_RES, bool BIG, bool STEM = false, int CB = 2, int PBW = 2>
+__global__ void __launch_bounds__(256 + 64 * NLOAD, (4 + NLOAD) / 4)
+    conv3x3_f16r_kernel(const _Float16* __restrict__ in, const _Float16* __restrict__ w, const float* __restrict__ bias, float* stream,
+                        _Float16* __restrict__ out, unsigned* __restrict__ sat, int cin, int cout, int S, int flags, StemPlanes<STEM> sp) {
+    conv3x3_mfma_v2_layer<_Float16, HAS_RES, BIG, STEM, CB, PBW, true>(in, w, bias, nullptr, out, stream, sat, cin, cout, S, flags, sp);
 }
 
 #ifdef CATTUS_STAMPS
@@ -1277,14 +1330,25 @@ __global__ void __launch_bounds__(512, 2)
 template <typename T>
 struct ConvV2 {  // conv3x3_mfma_v2_kernel: f32, bf16, single-term f16
     typedef T elem;
+    typedef const T* res_ptr;
     static constexpr bool HALF_ROWS = true;
     static constexpr int THREADS = 256 + 64 * NLOAD;
     static constexpr int lds(int, int) { return V2_LDS_TOTAL; }
     template <bool R, bool BIG, bool STEM, int CB, int PBW>
     static auto kernel() { return &conv3x3_mfma_v2_kernel<T, R, BIG, STEM, CB, PBW>; }
 };
+struct ConvF16R {  // conv3x3_f16r_kernel: the f16 instances of conv3x3_mfma_v2_kernel with the residual stream in f32 (`res` is the stream)
+    typedef _Float16 elem;
+    typedef float* res_ptr;
+    static constexpr bool HALF_ROWS = true;
+    static constexpr int THREADS = 256 + 64 * NLOAD;
+    static constexpr int lds(int, int) { return V2_LDS_TOTAL; }
+    template <bool R, bool BIG, bool STEM, int CB, int PBW>
+    static auto kernel() { return &conv3x3_f16r_kernel<R, BIG, STEM, CB, PBW>; }
+};
 struct ConvSplit {  // conv3x3_split_kernel (weights through the LDS ring): it has no 128-row workgroup
     typedef _Float16 elem;
+    typedef const _Float16* res_ptr;
     static constexpr bool HALF_ROWS = false;
     static constexpr int THREADS = 512;
     static constexpr int lds(int, int) { return SP_LDS_TOTAL; }
@@ -1293,6 +1357,7 @@ struct ConvSplit {  // conv3x3_split_kernel (weights through the LDS ring): it h
 };
 struct ConvSplitW {  // conv3x3_splitw_kernel (weights in a register ring)
     typedef _Float16 elem;
+    typedef const _Float16* res_ptr;
     static constexpr bool HALF_ROWS = true;
     static constexpr int THREADS = 512;
     static constexpr int lds(int cb, int pbw) { return sw_lds_total(cb, pbw); }  // 53,536 B on the 128-row tile: that one would do without the opt-in
@@ -1334,6 +1399,23 @@ static ConvTile conv_tile(uint32_t bpad, uint32_t slots, uint32_t cout, const Co
     return {cb, half_rows ? 1 : 2, half_rows ? grid * 2 : grid};
 }
 
+// One launch of family K: the instance whose template arguments equal the launch's key.
+template <class K>
+static void launch_conv_family(const void* in, const void* w, const float* bias, const void* res, bool has_res, void* out, uint32_t bpad, uint32_t cin,
+                               uint32_t cout, uint32_t S, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, const StemInput* stem, int flags,
+                               const ConvOpts& opts) {
+    typedef typename K::elem T;
+    const uint32_t slots = tower_slots(S);
+    const ConvTile tile = conv_tile(bpad, slots, cout, opts, K::HALF_ROWS);
+    for_each_conv<K>([&](auto kernel, int lds, auto r, auto big, auto stemv, auto cb, auto pbw) {
+        if (r != has_res || big != (slots == 128) || stemv != (stem != nullptr) || cb != tile.cb || pbw != tile.pbw) return;
+        StemPlanes<decltype(stemv)::value> sp;
+        if constexpr (decltype(stemv)::value) sp = {stem->planes, stem->n, stem->C, stem->w64};
+        hipExtLaunchKernelGGL(kernel, dim3(tile.grid), dim3(K::THREADS), lds, st, ev_start, ev_stop, 0, (const T*)in, (const T*)w, bias,
+                              (typename K::res_ptr)res, (T*)out, opts.saturated, (int)cin, (int)cout, (int)S, flags, sp);
+    });
+}
+
 void launch_conv3x3_mfma(Act act, const void* in, const void* w, const float* bias, const void* res, void* out,
                          uint32_t bpad, uint32_t cin, uint32_t cout, uint32_t S, hipStream_t st, hipEvent_t ev_start,
                          hipEvent_t ev_stop, const StemInput* stem, int flags, const ConvOpts& opts) {
@@ -1346,25 +1428,25 @@ void launch_conv3x3_mfma(Act act, const void* in, const void* w, const float* bi
         fprintf(stderr, "cattus: launch_conv3x3_mfma: CONV_W_FRAG needs cin >= 64 on a non-stem layer (got %u)\n", cin);
         abort();
     }
-    const uint32_t slots = tower_slots(S);
     const bool has_res = res && !stem;
     auto launch = [&](auto family) {
-        typedef decltype(family) K;
-        typedef typename K::elem T;
-        const ConvTile tile = conv_tile(bpad, slots, cout, opts, K::HALF_ROWS);
-        for_each_conv<K>([&](auto kernel, int lds, auto r, auto big, auto stemv, auto cb, auto pbw) {
-            if (r != has_res || big != (slots == 128) || stemv != (stem != nullptr) || cb != tile.cb || pbw != tile.pbw) return;
-            StemPlanes<decltype(stemv)::value> sp;
-            if constexpr (decltype(stemv)::value) sp = {stem->planes, stem->n, stem->C, stem->w64};
-            hipExtLaunchKernelGGL(kernel, dim3(tile.grid), dim3(K::THREADS), lds, st, ev_start, ev_stop, 0, (const T*)in, (const T*)w, bias,
-                                  (const T*)res, (T*)out, opts.saturated, (int)cin, (int)cout, (int)S, flags, sp);
-        });
+        launch_conv_family<decltype(family)>(in, w, bias, res, has_res, out, bpad, cin, cout, S, st, ev_start, ev_stop, stem, flags, opts);
     };
     if (wfrag) launch(ConvSplitW{});
     else if (act == Act::F16S) launch(ConvSplit{});
     else if (act == Act::BF16) launch(ConvV2<__bf16>{});
     else if (act == Act::F16) launch(ConvV2<_Float16>{});
     else launch(ConvV2<float>{});
+}
+
+void launch_conv3x3_f16r(const void* in, const void* w, const float* bias, float* stream, bool skip, void* copy, uint32_t bpad, uint32_t cin,
+                         uint32_t cout, uint32_t S, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, const StemInput* stem, bool last,
+                         const ConvOpts& opts) {
+    if (!opts.saturated || !stream || (!last && !copy) || (skip && stem)) {
+        fprintf(stderr, "cattus: launch_conv3x3_f16r: needs ConvOpts::saturated, a stream, a copy buffer unless the layer is the last, and no skip on the stem\n");
+        abort();
+    }
+    launch_conv_family<ConvF16R>(in, w, bias, stream, skip, copy, bpad, cin, cout, S, st, ev_start, ev_stop, stem, last ? CONV_OUT_F32 : 0, opts);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1913,6 +1995,7 @@ hipError_t prepare_device() {
     conv_opt_in<ConvV2<__bf16>>(err);
     conv_opt_in<ConvV2<float>>(err);
     conv_opt_in<ConvV2<_Float16>>(err);
+    conv_opt_in<ConvF16R>(err);
     conv_opt_in<ConvSplit>(err);
     conv_opt_in<ConvSplitW>(err);
     for_each_tower64<__bf16>([&](auto kernel, int lds, auto...) { lds_opt_in(err, kernel, lds); });

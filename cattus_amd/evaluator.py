@@ -30,6 +30,10 @@ _DTYPES = {"f32": DTYPE_F32, "bf16": DTYPE_BF16, "f16x2": DTYPE_F16X2, "f16": DT
 # beside _DTYPES, which stays the five dtypes it was; the constructor consults both.
 DTYPE_F32W = 5
 _DTYPES_WINO_F32 = {"f32w": DTYPE_F32W}
+# "f16r": the direct single-term f16 tower with the residual stream kept in f32 (CATTUS_DTYPE_F16R: opt-in, bits of its own, dtype f16's
+# coverage).  A table of its own again: the two above stay what they were.
+DTYPE_F16R = 6
+_DTYPES_F16R = {"f16r": DTYPE_F16R}
 
 # every symbol include/cattus_hip.h declares
 ABI_SYMBOLS = [
@@ -339,6 +343,9 @@ class HipEvaluator:
         board, at least one residual block, a multiple of 64 filters >= 128, tower_form "auto" or "winograd" (both mean it); anything else is refused.
         "f32w" is the f32-operand tower in the same form with the same coverage and the same refusals: the exact tower's stem, U = f32(G g G^T), f32 sums, no
         cap, no stream shift, ``saturated`` stays 0; bits of its own (not the exact tower's); ``verify`` / ``trace`` hold it to the f32 shadow like any other.
+        "f16r" (_DTYPES_F16R) is the direct single-term f16 tower with the residual stream kept in f32: dtype "f16"'s weights, shifts, calibration and coverage
+        (any board, any filter count), one launch per layer, bits of its own; tower_form "resident" is refused, the other forms (forms of the "f16x2" tower) mean "auto"; calibrated, it keeps
+        the BatchNorm estimate's shifts and takes only the headroom guard from the sample, as "f16w" does.
         tower_form: "auto" | "direct" | "winograd" | "winograd_f4" | "direct_splitk" (cattus_tower_form; None = "auto", or what CATTUS_WINOGRAD=0/1 in the
         environment says; "winograd_f4", the F(4x4,3x3) form, and "direct_splitk", the direct form with the K walk divided over a workgroup's waves
         for batches of a few leaves, are opt-in only: never what "auto" picks, and each has bits of its own; "resident" (TOWER_FORMS_RESIDENT)
@@ -368,7 +375,7 @@ class HipEvaluator:
         if switches is None:
             switches = {k: os.environ[k] for k in DIAG_SWITCHES if k in os.environ}
         self.tower_form = tower_form
-        cfg = EvalConfig(C.sizeof(EvalConfig), device, self.batch_size, self.plane_words, {**_DTYPES, **_DTYPES_WINO_F32}[dtype], flush_us, {**TOWER_FORMS, **TOWER_FORMS_RESIDENT}[tower_form], int(tail_leaves))
+        cfg = EvalConfig(C.sizeof(EvalConfig), device, self.batch_size, self.plane_words, {**_DTYPES, **_DTYPES_WINO_F32, **_DTYPES_F16R}[dtype], flush_us, {**TOWER_FORMS, **TOWER_FORMS_RESIDENT}[tower_form], int(tail_leaves))
         h = C.c_void_p()
         buf = C.create_string_buffer(blob, len(blob))
         text = ";".join(f"{k}={v}" for k, v in switches.items()).encode() if switches else None

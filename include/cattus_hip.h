@@ -95,6 +95,40 @@ typedef enum cattus_dtype {
      * below 64 leaves, other filter counts than 128 and 256; no counter or stamped run of the kernel was made: what binds its loop is
      * a supposition. */
     CATTUS_DTYPE_F32W = 5,
+    /* Direct single-term f16 with an F32 RESIDUAL STREAM (K1hr, conv3x3_f16r_kernel): CATTUS_DTYPE_F16's weights, per-output-channel
+     * power-of-two scales, [biases | inverse scales] and stream shifts, its kernel's roles and its MFMA sequence per accumulator -- only
+     * the epilogue differs.  Per layer, y = relu(fmaf(acc, 2^-s, bias) [+ skip]) under the pixel mask:
+     *   stem            writes the stream S as plain f32 rows holding y, not clamped, and its operand copy A = f16(min(y, 65504));
+     *   conv1 of a block reads A, writes the middle activation M as f16 rows: CATTUS_DTYPE_F16's layer (no skip, clamp, count);
+     *   conv2 of a block reads M, adds the F32 row of S (y = relu(fmaf(acc, 2^-s, bias) + S) in f32), writes y back to S in place and
+     *                   A = f16(min(y, 65504));
+     *   the last layer  writes S alone; the common f32 heads read it.
+     * Values beyond 65504 in a copy are counted in cattus_stats.saturated; the stream itself keeps them.  So the stream is never rounded
+     * to 11 bits, as under CATTUS_DTYPE_F16W, without that form's cost or coverage.  Bits of its own, anchored to CATTUS_DTYPE_F16's: a
+     * network without blocks, and point 1 of any network, have that dtype's bits; point 0 rounds to its point 0.  The bits do not depend
+     * on the tile.  Three lane buffers as before (S f32, A f16, M f16).
+     * Coverage: every shape CATTUS_DTYPE_F16 runs on the MFMA per-layer tower -- any board up to 11x11, any filter count, up to 128
+     * plane words, vhc + phc <= 32 (wider heads: CATTUS_E_UNSUPPORTED).  A SimpleTwoHeadedModel blob runs in f32, as under every dtype.
+     * tower_form: AUTO means this tower; DIRECT, WINOGRAD, WINOGRAD_F4 and DIRECT_SPLITK, forms of the F16X2 tower, are ignored;
+     * RESIDENT is CATTUS_E_UNSUPPORTED (no resident kernel keeps an f32 stream: the follow-up).  tail_leaves is ignored
+     * (cattus_hip_tail_leaves reports 0).  cattus_hip_time_tower reports 1 + 2 blocks launches.  Observation: the stream points (0,
+     * 2i + 2) are tapped from S in f32, times 2^-t_k, the middle points from M.  The stream shifts are CATTUS_DTYPE_F16's (they protect the
+     * f16 copy's small channels).  cattus_hip_create_calibrated is accepted as for CATTUS_DTYPE_F16, with CATTUS_DTYPE_F16W's rule, the
+     * stream being f32: the tower keeps the shifts of the BatchNorm estimate and takes from the sample the headroom guard, unchanged (a
+     * channel's shift is lowered while its measured largest |value| 2^t exceeds 4096), so a network whose estimate is right keeps its
+     * shifts and its bits; CATTUS_DTYPE_F16's measured lift of channels the estimate misses is not taken.
+     * Measured, first build (scripts/f16r_time.py -> profiles/f16r_first_build.txt; one process, the towers alternating; ms per step,
+     * F16R | F16 | F16W | F16X2 under AUTO): chess 20x256 at 64 leaves 0.369 | 0.354 | 0.495 | 0.602, at 128 0.576 | 0.544 | 0.676 |
+     * 1.024, at 256 0.939 | 0.855 | 1.238 | 1.180; chess 4x128 at 256 leaves 0.104 | 0.098 | 0.116 | 0.151; hex7 6x64 at 128 leaves
+     * 0.083 | 0.082 | not covered | 0.061 (resident).  So 1.01 - 1.10x CATTUS_DTYPE_F16's step time, inside the 12 % that two boxes
+     * differ by: no difference from F16 in speed, and 0.75 - 0.90x F16W's time.  Per leaf (profiles/f16r_numerics.txt) rms |dlogit|
+     * against float64 0.53x / 0.45x / 0.51x F16's on the chess 4x128 / chess 20x256 / hex7 6x64 fixtures (emulation, profiles/
+     * gate_f16r.json: 0.53 / 0.44 / 0.52).  Search level (256 searches of 800 simulations on chess 20x256 against the f32 search): 100.0 %
+     * of the moves equal, visit L1 mean 0.00006; F16 on the same searches 99.2 %, 0.00039, F16W 99.6 %, 0.00037.  RECOMMENDED wherever
+     * F16 or F16W is used today; not where a 64-filter resident form runs (F16X2's is 1.36x faster on hex7 6x64).  The estimate written
+     * before the run (+3 - 10 % on F16 by batch size) was met at its upper end.  Not measured: stamps, counters,
+     * other filter counts than 256 / 128 / 64, batches below 64 leaves, two evaluators on one device. */
+    CATTUS_DTYPE_F16R = 6,
 } cattus_dtype;
 /* Every dtype takes any network the blob format and the plane pack allow: up to 128 plane words per leaf (planes x plane_words),
  * e.g. AlphaZero's 119 chess planes. */

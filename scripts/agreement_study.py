@@ -3,7 +3,7 @@
 (tests/test_search_parity_gpu.py: 16 games):
     python scripts/agreement_study.py [GAMES=128] [PLIES=16] [SIMS=800] [chess20x256|hex7_6x64] [DTYPES=f16x2,bf16]
 (a dtype "f16x2w" is the f16x2 tower forced into its Winograd form, which an evaluator of this study's small batches would not pick;
-"f16w" is the dtype of that name, the single-term f16 tower in Winograd form)
+"f16w" is the dtype of that name, the single-term f16 tower in Winograd form; "f16r" the direct single-term f16 tower with an f32 residual stream)
 f32 plays GAMES games of chess 20x256 (or hex7 6x64, BASELINE config 2's net) (random 2-ply openings, greedy, noise off)
 for PLIES searched plies; each dtype under test searches the same positions (teacher-forced, trees carried over).
 Prints one JSON object per dtype."""
