@@ -352,6 +352,10 @@ enum class TowerKind {
     // in f32 (K1hr: conv3x3_f16r_kernel for the stem and every conv2, dtype f16's own layer for every conv1; f16r_rule.h has the buffer
     // plan): dtype f16's weights, scales, shifts and coverage, bits of its own from point 2 on, always one launch per layer
     PerLayerStream,
+    // dtype f16r_resident (Act::F16 with this kind, and no other kind for that dtype): PerLayerStream's tower of a network with <= 64 filters
+    // in one LDS-resident launch (K1hr resident: tower64_stream_kernel; t64r_rule.h) -- the f32 stream in the owning lanes' registers, dtype
+    // f16r's weights, scales, shifts, calibration and bits; Resident64's coverage, workgroup shapes and switches; observed on PerLayerStream
+    Resident64Stream,
 };
 struct TowerPlan {
     TowerKind kind = TowerKind::Generic;
@@ -361,6 +365,8 @@ struct TowerPlan {
     // a layer has more tiles than the device has CUs (CATTUS_WINO_PERSIST=0: per-layer launches) -- for the batches one_launch_now() admits
     bool one_launch = false;
     bool tuned() const { return kind != TowerKind::Simple && kind != TowerKind::Generic; }  // the MFMA NHWC towers
+    bool resident() const { return kind == TowerKind::Resident64 || kind == TowerKind::Resident64Split || kind == TowerKind::Resident64Stream; }  // one launch, activations in LDS
+    bool f32_stream() const { return kind == TowerKind::PerLayerStream || kind == TowerKind::Resident64Stream; }  // dtype f16r's arithmetic (f16r_rule.h)
     bool wino() const { return kind == TowerKind::Wino16 || kind == TowerKind::Wino4 || kind == TowerKind::WinoF4 || kind == TowerKind::WinoF16 || kind == TowerKind::WinoF32; }  // f32 rows between the layers
 };
 
@@ -593,7 +599,7 @@ int build(cattus_eval* e, const float* p, const Calibration* cal) {
         const double headroom = plan.kind == TowerKind::WinoF4 ? WINOF4_CAL_HEADROOM : STREAM_CAL_HEADROOM;
         // (the f16w tower's stream is f32: calibrated, it keeps the estimate's shifts and takes the measured guard alone -- weight_layout.h;
         // so does the f16r tower, whose stream is f32 as well: its shifts serve the f16 operand copy, and a seeded net keeps its shifts and bits)
-        if (cal && (plan.kind == TowerKind::WinoF16 || plan.kind == TowerKind::PerLayerStream))
+        if (cal && (plan.kind == TowerKind::WinoF16 || plan.f32_stream()))
             e->stream_shifts = calibrated_stream_shifts_f32_stream(choose_stream_shift(d, p, &e->stream_shift, STREAM_NO_CEILING), cal->abs_max, headroom);
         else if (cal) e->stream_shifts = calibrated_stream_shifts(cal->s2, cal->abs_max, headroom), e->stream_shift = stream_shift_global(cal->s2);
         else e->stream_shifts = choose_stream_shift(d, p, &e->stream_shift, plan.kind == TowerKind::WinoF4 ? WINOF4_STREAM_CEILING : STREAM_NO_CEILING);
@@ -692,6 +698,14 @@ int build(cattus_eval* e, const float* p, const Calibration* cal) {
         const auto tl = layer_table([](const ConvLayer& c, int res, bool) { return Tower64Layer{c.w.p, c.b.as<float>(), res, 0}; });
         if ((rc = e->t64_layers.upload(tl.data(), tl.size() * sizeof(Tower64Layer)))) return rc;
     }
+    if (plan.kind == TowerKind::Resident64Stream) {  // t64r_rule.h's table: the skip flag per layer (the last-layer flag follows from nlayers)
+        std::vector<Tower64Layer> tl;
+        for (uint32_t l = 0; l < t64r_layers(d.blocks); l++) {
+            const ConvLayer& c = l == 0 ? e->stem : (l & 1) ? *e->c1[(l - 1) / 2] : *e->c2[(l - 1) / 2];
+            tl.push_back(Tower64Layer{c.w.p, c.b.as<float>(), t64r_layer(l, d.blocks).skip ? 1 : 0, 0});
+        }
+        if ((rc = e->t64_layers.upload(tl.data(), tl.size() * sizeof(Tower64Layer)))) return rc;
+    }
     if (plan.kind == TowerKind::Resident64Split) {
         const auto tl = layer_table([](const ConvLayer& c, int res, bool stem) { return Tower64SplitLayer{c.w.p, c.b.as<float>(), res, stem ? 1 : 2}; });
         if ((rc = e->t64_layers.upload(tl.data(), tl.size() * sizeof(Tower64SplitLayer)))) return rc;
@@ -776,7 +790,7 @@ struct Forward {
         TapSource s{};
         s.C = F, s.hw = e->hw, s.slots = e->slots, s.pitch = FP;
         if (!e->plan.tuned()) s.layout = TAP_NCHW_F32;
-        else if (e->plan.kind == TowerKind::PerLayerStream) return f16r_tap_source(l, F, e->hw, e->slots, FP);
+        else if (e->plan.f32_stream()) return f16r_tap_source(l, F, e->hw, e->slots, FP);
         else if (e->plan.wino()) s.layout = TAP_ROWS_WINO_F32;
         else if (e->act == Act::F32 || (act_f16_family(e->act) && l == 2 * d.blocks)) s.layout = TAP_ROWS_F32;
         else s.layout = e->act == Act::BF16 ? TAP_ROWS_BF16 : e->act == Act::F16 ? TAP_ROWS_F16 : TAP_ROWS_F16X2;
@@ -836,18 +850,33 @@ struct Forward {
     }
 
     // bf16: the head convs fused, nullptr; f16: the tower's output as plain f32 rows in `a` for the f32 head kernels
+    // 128-row workgroups; for 64-slot boards one board per workgroup while that leaves no CU with two of them
+    int resident64_ch(uint32_t rows) const {
+        if (e->t64_force_ch) return e->t64_force_ch == 4 && e->slots == 64 ? 4 : 2;  // A/B runs, the row-split test
+        return e->slots == 64 && rows / 64 <= 256 ? 4 : 2;
+    }
+
     const void* resident64() {
         Tower64Args ta{};
         const bool f16 = e->act == Act::F16;
         resident_args(ta, !f16);
         if (f16) ta.out = a, ta.sat = e->conv_opts.saturated;
         const uint32_t rows = nb * e->slots;
-        // 128-row workgroups; for 64-slot boards one board per workgroup while that leaves no CU with two of them
         hipEvent_t s0 = ev(), s1 = ev();
-        int ch = e->slots == 64 && rows / 64 <= 256 ? 4 : 2;
-        if (e->t64_force_ch) ch = e->t64_force_ch == 4 && e->slots == 64 ? 4 : 2;  // A/B runs, the row-split test
-        launch_tower64(e->act, ta, rows, ch, e->t64_layer_steps, st, s0, s1);
+        launch_tower64(e->act, ta, rows, resident64_ch(rows), e->t64_layer_steps, st, s0, s1);
         return f16 ? ta.out : nullptr;
+    }
+
+    // dtype f16r_resident: the tower's output, the f32 stream behind the last layer, as plain f32 rows in the stream's buffer for the f32 head kernels
+    const void* resident64_stream() {
+        void* const buf[3] = {L.a.p, L.t.p, L.y.p};
+        Tower64Args ta{};
+        resident_args(ta, false);
+        ta.out = buf[f16r_head_input()], ta.sat = e->conv_opts.saturated;
+        const uint32_t rows = nb * e->slots;
+        hipEvent_t s0 = ev(), s1 = ev();
+        launch_tower64_stream(ta, rows, resident64_ch(rows), e->t64_layer_steps, st, s0, s1);
+        return ta.out;
     }
 
     // CATTUS_T64S_HEADS=0: the tower's output as plain f32 rows in `a` for the f32 head kernels
@@ -1003,8 +1032,8 @@ uint32_t padded_boards(const cattus_eval* e, uint32_t n) {
 int enqueue_forward(cattus_eval* e, Lane& L, const uint64_t* d_planes, uint32_t n, float* d_policy, float* d_value, hipStream_t st, TowerTimer* tt = nullptr,
                     const Observer* obs = nullptr) {
     Forward f{e, L, d_planes, n, padded_boards(e, n), d_policy, d_value, st, tt, obs};
-    const bool resident = e->plan.kind == TowerKind::Resident64 || e->plan.kind == TowerKind::Resident64Split;
-    switch (obs && resident ? TowerKind::PerLayer : e->plan.kind) {  // observed: the resident towers' per-layer twin (upload_conv: one layout for both)
+    // observed: the resident towers' per-layer twin (upload_conv: one layout for both) -- the f32-stream one's is PerLayerStream
+    switch (obs && e->plan.resident() ? (e->plan.f32_stream() ? TowerKind::PerLayerStream : TowerKind::PerLayer) : e->plan.kind) {
         case TowerKind::Simple: f.simple(); break;
         case TowerKind::Generic: f.heads_generic(f.generic()); break;
         case TowerKind::PerLayer: f.heads_mfma(f.per_layer()); break;
@@ -1012,6 +1041,7 @@ int enqueue_forward(cattus_eval* e, Lane& L, const uint64_t* d_planes, uint32_t 
         case TowerKind::DirectSplitK: f.heads_mfma(f.per_layer()); break;  // the stem through conv_mfma, every layer behind it through conv_splitk
         case TowerKind::Resident64: f.heads_mfma(f.resident64()); break;
         case TowerKind::Resident64Split: f.heads_mfma(f.resident64_split()); break;
+        case TowerKind::Resident64Stream: f.heads_mfma(f.resident64_stream()); break;
         case TowerKind::Wino16:
         case TowerKind::Wino4:
         case TowerKind::WinoF4:
@@ -1332,6 +1362,7 @@ CATTUS_API const char* cattus_hip_tower_kernel(const cattus_eval* e) {
         case TowerKind::Generic: return "conv3x3_generic_kernel";
         case TowerKind::Resident64: return "tower64_lds_kernel";
         case TowerKind::Resident64Split: return "tower64_split_kernel";
+        case TowerKind::Resident64Stream: return "tower64_stream_kernel";
         case TowerKind::Wino16: return "conv3x3_wino_kernel";
         case TowerKind::Wino4: return one_launch_now(e, e->bpad) ? "tower_wino4_kernel" : "conv3x3_wino4_kernel";
         case TowerKind::WinoF4: return "conv3x3_winof4_kernel";
@@ -1429,7 +1460,10 @@ int resolve_plan(const cattus_net_desc& d, const cattus_eval_config& cfg, const 
     // the two 1x1 head convs share one 32-row MFMA tile.  Wider heads take the generic f32 path (one thread
     // per output, same arithmetic order), which otherwise serves as a checker only (CATTUS_FORCE_GENERIC=1).
     const bool simple = d.filters == 0, tuned = !simple && d.vhc + d.phc <= 32 && !sw.starts("CATTUS_FORCE_GENERIC", '1');
-    if (!tuned && act != Act::F32)
+    // the LDS-resident bf16 / f16 tower's coverage (tower64_lds_kernel, tower64_stream_kernel): at most 64 padded filters, planes it expands itself
+    const bool resident = tuned && fpad == 64 && !sw.starts("CATTUS_TOWER64", '0');
+    const bool resident64 = resident && cpad0 == 64;
+    if (!tuned && act != Act::F32 && cfg.dtype != CATTUS_DTYPE_F16R_RESIDENT)  // (f16r_resident refuses below, under its own name)
         return fail(CATTUS_E_UNSUPPORTED, "bf16 / f16 / f16x2 need the MFMA tower: value + policy head channels <= 32 (got %u + %u)", d.vhc, d.phc);
     // dtype f16w: the single-term f16 Winograd tower and nothing else -- AUTO and WINOGRAD both mean it, every other form and every
     // shape it does not cover is refused (never other bits under this name); a SimpleTwoHeadedModel runs in f32 as under every dtype
@@ -1457,12 +1491,23 @@ int resolve_plan(const cattus_net_desc& d, const cattus_eval_config& cfg, const 
     }
     // dtype f16r: the per-layer direct f16 tower with an f32 residual stream and nothing else -- every shape dtype f16 runs on the MFMA
     // per-layer tower (wider heads were refused above: the generic path is f32); AUTO means it, the forms 1-4 are ignored (they name forms of the
-    // f16x2 tower; dtype f16 ignores DIRECT alike), RESIDENT is refused (no resident kernel keeps an f32 stream yet: the follow-up), tail_leaves is ignored
+    // f16x2 tower; dtype f16 ignores DIRECT alike), RESIDENT is refused (the one-launch form of this tower is a dtype of its own, f16r_resident, below), tail_leaves is ignored
     if (cfg.dtype == CATTUS_DTYPE_F16R && !simple) {
         if (cfg.tower_form == CATTUS_TOWER_RESIDENT)
-            return fail(CATTUS_E_UNSUPPORTED, "dtype f16r has no LDS-resident form: no resident kernel keeps an f32 residual stream (tower_form AUTO)");
+            return fail(CATTUS_E_UNSUPPORTED, "dtype f16r is the per-layer tower (tower_form AUTO): its one-launch LDS-resident form is dtype f16r_resident");
         *plan = TowerPlan();
         plan->kind = TowerKind::PerLayerStream;
+        return CATTUS_OK;
+    }
+    // dtype f16r_resident: dtype f16r's arithmetic, bit for bit, as a demand for the one-launch LDS-resident form and nothing else -- exactly the
+    // evaluators on which dtype f16 accepts tower_form RESIDENT (`resident64` above: one predicate for both); AUTO and RESIDENT both mean it, the
+    // forms 1-4 are ignored as under f16r, tail_leaves is ignored; anything the form does not cover is refused, never other bits under this name
+    if (cfg.dtype == CATTUS_DTYPE_F16R_RESIDENT && !simple) {
+        if (!resident64)
+            return fail(CATTUS_E_UNSUPPORTED, "dtype f16r_resident is dtype f16r in the one-launch LDS-resident form: at most 64 filters, at most 64 planes, value + policy head channels <= 32 "
+                                              "(and no CATTUS_TOWER64=0); dtype f16r runs every other shape per layer");
+        *plan = TowerPlan();
+        plan->kind = TowerKind::Resident64Stream;
         return CATTUS_OK;
     }
     // the 4-frequency kernel wherever it covers the layer shape (filters a multiple of 64), else the 16-frequency one (128)
@@ -1488,8 +1533,7 @@ int resolve_plan(const cattus_net_desc& d, const cattus_eval_config& cfg, const 
         p.kind = TowerKind::DirectSplitK;
         return CATTUS_OK;
     }
-    const bool resident = tuned && fpad == 64 && !sw.starts("CATTUS_TOWER64", '0');
-    const bool resident64 = resident && cpad0 == 64, resident64_split = resident && cpad0 == 32 && p.w_frag && 1 + 2 * d.blocks <= (uint32_t)T64S_MAX_LAYERS;
+    const bool resident64_split = resident && cpad0 == 32 && p.w_frag && 1 + 2 * d.blocks <= (uint32_t)T64S_MAX_LAYERS;
     // RESIDENT: the one-launch LDS-resident tower, a demand: what AUTO gives bf16 and f16x2 on these shapes, and for f16 -- only when asked
     // for -- bf16's kernel on bf16's shapes with the per-layer f16 tower's bits; a SimpleTwoHeadedModel runs in f32 as under every form
     if (cfg.tower_form == CATTUS_TOWER_RESIDENT && !simple) {
@@ -1547,7 +1591,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
         return fail(CATTUS_E_INVALID, "plane_words %u cannot hold a %ux%u board", cfg->plane_words, d.board, d.board);
     if (d.planes * cfg->plane_words > 128) return fail(CATTUS_E_UNSUPPORTED, "more than 128 plane words per leaf");
     if (cfg->dtype != CATTUS_DTYPE_F32 && cfg->dtype != CATTUS_DTYPE_BF16 && cfg->dtype != CATTUS_DTYPE_F16X2 && cfg->dtype != CATTUS_DTYPE_F16 &&
-        cfg->dtype != CATTUS_DTYPE_F16W && cfg->dtype != CATTUS_DTYPE_F32W && cfg->dtype != CATTUS_DTYPE_F16R)
+        cfg->dtype != CATTUS_DTYPE_F16W && cfg->dtype != CATTUS_DTYPE_F32W && cfg->dtype != CATTUS_DTYPE_F16R && cfg->dtype != CATTUS_DTYPE_F16R_RESIDENT)
         return fail(CATTUS_E_INVALID, "unknown dtype %u", cfg->dtype);
     if (!simple && (size_t)d.phc * d.board * d.board * 8 * 4 > 64 * 1024) return fail(CATTUS_E_UNSUPPORTED, "policy head too wide for the FC kernel");
 
@@ -1600,7 +1644,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
     e->act = simple ? Act::F32
              : cfg->dtype == CATTUS_DTYPE_BF16 ? Act::BF16
              : cfg->dtype == CATTUS_DTYPE_F16X2 ? Act::F16S
-             : cfg->dtype == CATTUS_DTYPE_F16 || cfg->dtype == CATTUS_DTYPE_F16W || cfg->dtype == CATTUS_DTYPE_F16R ? Act::F16  // f16w: the direct f16 stem, f16r: f16 operands; resolve_plan chooses their towers
+             : cfg->dtype == CATTUS_DTYPE_F16 || cfg->dtype == CATTUS_DTYPE_F16W || cfg->dtype == CATTUS_DTYPE_F16R || cfg->dtype == CATTUS_DTYPE_F16R_RESIDENT ? Act::F16  // f16w: the direct f16 stem, f16r / f16r_resident: f16 operands; resolve_plan chooses their towers
                                               : Act::F32;  // f32w too: the direct f32 stem and f32 rows; resolve_plan chooses its tower
     // the tuned towers' layout: whole workgroups of boards, filters in whole 64-channel groups (zero channels), the planes in whole
     // 128-byte rows; the other towers pad nothing
@@ -1716,7 +1760,7 @@ int create_calibrated_impl(const void* weights, size_t nbytes, const cattus_eval
     uint32_t filters = 0;  // 0: SimpleTwoHeadedModel (or no blob at all, which create_impl refuses)
     if (nbytes >= HEADER_BYTES) memcpy(&filters, (const char*)weights + 8 + 5 * 4, 4);
     // only the f16 towers shift their stream: everything else is cattus_hip_create
-    if ((cfg->dtype != CATTUS_DTYPE_F16X2 && cfg->dtype != CATTUS_DTYPE_F16 && cfg->dtype != CATTUS_DTYPE_F16W && cfg->dtype != CATTUS_DTYPE_F16R) || filters == 0) return create_impl(weights, nbytes, cfg, switches, out);
+    if ((cfg->dtype != CATTUS_DTYPE_F16X2 && cfg->dtype != CATTUS_DTYPE_F16 && cfg->dtype != CATTUS_DTYPE_F16W && cfg->dtype != CATTUS_DTYPE_F16R && cfg->dtype != CATTUS_DTYPE_F16R_RESIDENT) || filters == 0) return create_impl(weights, nbytes, cfg, switches, out);
     cattus_eval_config mcfg{};
     mcfg.struct_size = sizeof mcfg, mcfg.device = cfg->device, mcfg.max_batch = std::min(n, 256u), mcfg.plane_words = cfg->plane_words;
     mcfg.dtype = CATTUS_DTYPE_F32, mcfg.flush_us = cfg->flush_us, mcfg.tower_form = CATTUS_TOWER_AUTO;
@@ -2278,7 +2322,7 @@ CATTUS_API int cattus_hip_time_tower(cattus_eval* e, uint32_t n, uint32_t reps, 
     HIP_TRY(hipSetDevice(e->device));
     // (the one-launch Winograd tower is reported per LAYER: its duration + the stem's over 1 + 2 blocks, so that a caller's
     // flops-per-launch arithmetic does not change with how the layers are launched)
-    const uint32_t per_fwd = e->plan.kind == TowerKind::Resident64 || e->plan.kind == TowerKind::Resident64Split ? 1 : 1 + 2 * e->d.blocks;
+    const uint32_t per_fwd = e->plan.resident() ? 1 : 1 + 2 * e->d.blocks;
     TowerTimer tt;
     tt.ev.resize((size_t)2 * per_fwd);
     for (auto& ev : tt.ev) HIP_TRY(hipEventCreate(&ev));

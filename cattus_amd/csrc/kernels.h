@@ -11,6 +11,7 @@
 #include "winof4_rule.h"  // the Winograd F(4x4, 3x3) form: matrices, transforms, geometry, cap, U index
 #include "splitk_rule.h"  // the split-K direct form: ways, ranges, reduction order, grid map, LDS plan
 #include "f16r_rule.h"    // dtype f16r: the epilogue with an f32 residual stream, the lane buffers' roles, the tap layout per point
+#include "t64r_rule.h"    // dtype f16r_resident: that tower in one LDS-resident launch -- who owns an element, the LDS buffers, the layer table
 
 namespace cattus {
 
@@ -248,6 +249,12 @@ struct Tower64Args {
 // out); anything else aborts.
 void launch_tower64(Act act, const Tower64Args& args, uint32_t rows, int ch, bool layer_steps, hipStream_t st,
                     hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+// K1hr resident (dtype f16r_resident; tower64_stream_kernel; t64r_rule.h has the ownership map, the LDS buffers and the layer table): the
+// Act::F16 launch above -- its arguments, layers (dtype f16r's = dtype f16's weights and [biases | inverse scales]; Tower64Layer::res as
+// t64r_layer().skip), workgroup shapes and LDS plan -- with the residual stream kept in f32 in the owning lanes' registers: the bits of
+// the per-layer f16r tower (launch_conv3x3_f16r and dtype f16's conv1).  args.sat and args.out required, no fused heads; anything else aborts.
+void launch_tower64_stream(const Tower64Args& args, uint32_t rows, int ch, bool layer_steps, hipStream_t st, hipEvent_t ev_start = nullptr,
+                           hipEvent_t ev_stop = nullptr);
 
 // ---- K1rs resident, split precision: the whole tower of a <= 64-filter f16x2 network in one launch (see kernels.hip) ----
 struct Tower64SplitLayer {

@@ -10,6 +10,7 @@
 //                                                       weights from L2 into a register ring, activations through LDS
 //       conv3x3_split<HAS_RES, BIG, STEM, CB>           its first form, both operands through LDS (CATTUS_SPLIT_W=0; bit-identical)
 //   K1r tower64_lds<CH, BIG>                            whole tower of a <= 64-filter bf16 network in one launch, activations in LDS
+//       tower64_stream<CH, BIG, LS>                     K1hr in that launch: dtype f16r's tower with the f32 stream in registers (dtype f16r_resident, t64r_rule.h)
 //   K1g conv3x3_generic                                 same arithmetic, any shape, SIMT f32 (checker; wide heads)
 //   K3  head_conv, K4 + K5 head_fc_pair                 1x1 head convs; value FC1 + FC2 + tanh and policy FC (MFMA)
 //       head_conv1x1, value_fc1, value_fc2_tanh, policy_fc   the same on the generic path (SIMT f32)
@@ -1482,10 +1483,18 @@ constexpr int R_LDS_W = 0;                    // 3 x 24 KiB
 // there is no room for zero rows: pixel slot 63, which such a board does not use, is kept zero and serves as one.
 constexpr int tower64_lds_bytes(int ch, bool ls) { return ls ? 6 * V2_SLAB + 2 * 64 * 128 : 3 * V2_SLAB + 2 * ((256 / ch) * 128 + 256); }
 
-template <typename T, int CH, bool BIG, bool LS = false>
-__global__ void __launch_bounds__(512, 2) tower64_lds_kernel(Tower64Args A) {
+// STREAM (T = _Float16 only; K1hr resident, dtype f16r_resident, t64r_rule.h): dtype f16r's tower in this launch -- the residual stream y
+// in f32, never rounded and never clamped, in the registers of the lane that owns the element (t64r_own: a lane finishes the same
+// elements in every layer, so the lane that adds a skip element is the lane that produced it); LDS holds what the f16 tower's holds,
+// byte for byte: buffer 0 the operand copy f16(min(y, 65504)), buffer 1 the planes and then a block's middle activation.  Every
+// element is finished by f16r_finish, as in conv3x3_f16r_kernel; a conv1 is the f16 tower's layer.  Loader waves, weight ring, plane
+// expansion, address tables and fragment pipeline are shared: only the f16 epilogue branches on STREAM.
+// The body of the two __global__ functions below.
+template <typename T, int CH, bool BIG, bool LS, bool STREAM>
+__device__ __forceinline__ void tower64_lds_tower(const Tower64Args A) {
     static_assert(NLOAD == 4, "512 threads: four consumer and four loader waves");
     static_assert(!LS || CH == 4, "layer steps: one board per workgroup only");
+    static_assert(!STREAM || std::is_same<T, _Float16>::value, "the f32 residual stream belongs to the single-term f16 tower");
     constexpr int R_LDS_ACT = (LS ? 6 : 3) * V2_SLAB;
     static_assert(sizeof(T) == 2, "128-byte rows of 64 channels");
     // single-term f16 tower (conv3x3_mfma_v2_kernel<_Float16>'s layers): weights pre-scaled per output channel, L.bias = [64 biases | 64
@@ -1497,6 +1506,7 @@ __global__ void __launch_bounds__(512, 2) tower64_lds_kernel(Tower64Args A) {
     static_assert(CH == 2 || CH == 4, "128 or 64 rows per workgroup");
     constexpr int CB = 1;                // 32-cout blocks per consumer wave
     constexpr int NPB = CH == 4 ? 1 : 2; // 32-pixel blocks per consumer wave
+    static_assert(ROWS == t64r_rows(CH) && CB == T64R_CB && NPB == t64r_npb(CH), "t64r_rule.h states this workgroup");
     static_assert(!(BIG && CH == 4), "a 128-slot board needs 128 rows in one workgroup");
     constexpr int ZERO_OFF = LS ? 63 * 128 : ROWS * 128;    // the zero row of a buffer (padding pixels read it): behind its rows / slot 63
     constexpr int ACT_BYTES = LS ? ROWS * 128 : ZERO_OFF + 256;  // buffer stride (not LS: a 256-byte zero area, device_common.h)
@@ -1664,11 +1674,21 @@ __global__ void __launch_bounds__(512, 2) tower64_lds_kernel(Tower64Args A) {
     int opaque = 0;
     frag wa[4];       // head conv weights of this lane's head channel row
     f32x4 hbias[4];   // head conv bias of the 16 head channels this lane's accumulator holds
+    // tower64_stream_kernel: the f32 residual stream of the elements this lane owns (t64r_own), across the layer loop; pixel slots off the board stay 0
+    f32x16 sreg[CB][NPB];
+    if constexpr (STREAM) {
+#pragma unroll
+        for (int i = 0; i < CB; i++)
+#pragma unroll
+            for (int j = 0; j < NPB; j++)
+#pragma unroll
+                for (int e = 0; e < 16; e++) sreg[i][j][e] = 0.0f;
+    }
     for (int layer = 0; layer < nlayers; layer++) {
         const Tower64Layer L = A.layers[layer];
         // buffers: the stem reads 1 and writes 0; a block's first conv reads 0 and writes 1, its second reads 1,
-        // adds 0 (the block input) and writes 0
-        const int in_buf = (layer & 1) ? 0 : 1;
+        // adds 0 (the block input; tower64_stream_kernel: the lane's stream registers instead) and writes 0
+        const int in_buf = t64r_reads((uint32_t)layer);
         const int ibase = R_LDS_ACT + in_buf * ACT_BYTES;
         const int obase = R_LDS_ACT + (1 - in_buf) * ACT_BYTES;
         // L.bias comes out of a table in memory, so the compiler cannot tell its address space: loaded through a
@@ -1808,9 +1828,39 @@ __global__ void __launch_bounds__(512, 2) tower64_lds_kernel(Tower64Args A) {
         if constexpr (F16T) {
             // the per-layer f16 epilogue in its order: times the inverse scale plus bias (exact scale: a power of two), + skip, ReLU with
             // the pixel mask, the clamp counted, one rounding to f16 -- the last layer instead as plain f32 rows for the f32 head kernels
-            const bool last = layer == nlayers - 1;
+            // STREAM: that epilogue serves the conv1 layers alone (no skip, never the last); the stem and every conv2 are finished here, by
+            // f16r_rule.h's f16r_finish per element -- the skip from and y to the lane's stream registers, then y's f16 operand copy to the
+            // output buffer (counted where clamped), or, on the last layer, y alone as f32 rows for the f32 head kernels.  Both addresses
+            // come from t64r_own, the map that names the element a register holds in every layer alike.
+            const T64rLayer rl = t64r_layer((uint32_t)layer, t64r_blocks((uint32_t)nlayers));
+            const bool stream_layer = STREAM && rl.stream;
+            if (stream_layer) {
+                unsigned nsat = 0;
+                const int lane_now = lane + opaque;  // (0: keeps the sixteen addresses below from being hoisted out of the layer loop, where the stream needs the registers)
+#pragma unroll
+                for (int cb = 0; cb < CB; cb++)
+#pragma unroll
+                    for (int pb = 0; pb < NPB; pb++)
+#pragma unroll
+                        for (int g = 0; g < 4; g++) {
+                            const T64rOwn own = t64r_own(CH, wave, lane_now, cb, pb, g * 4);  // elements g*4 .. g*4+3: four consecutive channels
+                            f32x4 yv;
+                            tx4 cv;
+#pragma unroll
+                            for (int q = 0; q < 4; q++) {
+                                const F16rOut o = f16r_finish(acc[cb][pb][g * 4 + q], dsv[cb][g][q], biasv[cb][g][q], sreg[cb][pb][g * 4 + q], rl.skip, pvalid[pb]);
+                                sreg[cb][pb][g * 4 + q] = o.stream;
+                                yv[q] = o.stream, cv[q] = o.copy, nsat += o.counted ? 1u : 0u;
+                            }
+                            if (rl.last) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(A.out) + t64r_out_index((size_t)row0, own)) = yv;
+                            else *reinterpret_cast<tx4*>(smem + obase + t64r_lds_offset(own)) = cv;
+                        }
+                if (!rl.last && nsat) atomicAdd(A.sat, nsat);  // note_saturation's rule: one atomic add on the clamp path only
+            } else {  // (not indented: the code as it was)
+            const int lres = STREAM ? 0 : L.res;
+            const bool last = !STREAM && layer == nlayers - 1;
             tx4 rv[CB][NPB][4];
-            if (L.res) {  // the block input lives in the buffer being overwritten: same addresses, all read first
+            if (lres) {  // the block input lives in the buffer being overwritten: same addresses, all read first
 #pragma unroll
                 for (int cb = 0; cb < CB; cb++)
 #pragma unroll
@@ -1829,7 +1879,7 @@ __global__ void __launch_bounds__(512, 2) tower64_lds_kernel(Tower64Args A) {
                         for (int j = 0; j < 8; j++) {
                             const int g = g2 * 2 + (j >> 2), q = j & 3;
                             float v = __builtin_fmaf(acc[cb][pb][g * 4 + q], dsv[cb][g][q], biasv[cb][g][q]);
-                            if (L.res) v = v + (float)rv[cb][pb][g][q];
+                            if (lres) v = v + (float)rv[cb][pb][g][q];
                             y[j] = pvalid[pb] && v > 0.0f ? v : 0.0f;
                         }
                         if (last) {
@@ -1847,6 +1897,7 @@ __global__ void __launch_bounds__(512, 2) tower64_lds_kernel(Tower64Args A) {
                             *reinterpret_cast<tx4*>(smem + eoff[cb][pb][g2 * 2 + gg]) = ov;
                         }
                     }
+            }
         } else {  // bf16 (not indented: the code as it was)
         // two code paths (uniform branch), packed f32 arithmetic: the MFMA pipes idle during an epilogue, so its
         // instruction count is what it costs
@@ -1959,15 +2010,42 @@ __global__ void __launch_bounds__(512, 2) tower64_lds_kernel(Tower64Args A) {
     STAMP_FLUSH(wave);
 }
 
-// Every instance of element type T (__bf16, _Float16) that exists, f(kernel, LDS bytes, CH, BIG, LS): one board per workgroup (CH = 4) on
-// 64-slot boards only, one barrier per layer (LS) with CH = 4 only.
+template <typename T, int CH, bool BIG, bool LS = false>
+__global__ void __launch_bounds__(512, 2) tower64_lds_kernel(Tower64Args A) {
+    tower64_lds_tower<T, CH, BIG, LS, false>(A);
+}
+
+// K1hr resident (dtype f16r_resident): the f16 tower above with the residual stream in f32, in the owning lanes' registers
+template <int CH, bool BIG, bool LS = false>
+__global__ void __launch_bounds__(512, 2) tower64_stream_kernel(Tower64Args A) {
+    tower64_lds_tower<_Float16, CH, BIG, LS, true>(A);
+}
+
+// Every instance that exists, f(kernel, LDS bytes, CH, BIG, LS): one board per workgroup (CH = 4) on 64-slot boards only, one barrier per
+// layer (LS) with CH = 4 only.  T: the element type of tower64_lds_kernel (__bf16, _Float16), or Tower64Stream for tower64_stream_kernel.
+struct Tower64Stream {};
 template <typename T, class F>
 static void for_each_tower64(F&& f) {
     each_int<2, 4>([&](auto ch) { each_bool([&](auto big) { each_bool([&](auto ls) {
         constexpr int CH = decltype(ch)::value;
         constexpr bool BIG = decltype(big)::value, LS = decltype(ls)::value;
-        if constexpr (CH == 4 ? !BIG : !LS) f(&tower64_lds_kernel<T, CH, BIG, LS>, tower64_lds_bytes(CH, LS), ch, big, ls);
+        if constexpr (CH == 4 ? !BIG : !LS) {
+            if constexpr (std::is_same<T, Tower64Stream>::value) f(&tower64_stream_kernel<CH, BIG, LS>, tower64_lds_bytes(CH, LS), ch, big, ls);
+            else f(&tower64_lds_kernel<T, CH, BIG, LS>, tower64_lds_bytes(CH, LS), ch, big, ls);
+        }
     }); }); });
+}
+
+// the instance of family T for (S, ch, layer_steps) -- one rule for tower64_lds_kernel and tower64_stream_kernel
+template <typename T>
+static void launch_tower64_of(const Tower64Args& args, uint32_t rows, int ch, bool layer_steps, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
+    const bool want_big = tower_slots(args.S) == 128;
+    const int want_ch = ch == 4 && !want_big ? 4 : 2;
+    const bool want_ls = want_ch == 4 && layer_steps && args.S * args.S <= 63;
+    for_each_tower64<T>([&](auto kernel, int lds, auto c, auto big, auto ls) {
+        if (c == want_ch && big == want_big && ls == want_ls)
+            hipExtLaunchKernelGGL(kernel, dim3(rows / (256 / c)), dim3(512), lds, st, ev_start, ev_stop, 0, args);
+    });
 }
 
 void launch_tower64(Act act, const Tower64Args& args, uint32_t rows, int ch, bool layer_steps, hipStream_t st, hipEvent_t ev_start,
@@ -1976,15 +2054,16 @@ void launch_tower64(Act act, const Tower64Args& args, uint32_t rows, int ch, boo
         fprintf(stderr, "cattus: launch_tower64: bf16, or f16 with Tower64Args::sat and ::out and no fused heads\n");
         abort();
     }
-    const bool want_big = tower_slots(args.S) == 128;
-    const int want_ch = ch == 4 && !want_big ? 4 : 2;
-    const bool want_ls = want_ch == 4 && layer_steps && args.S * args.S <= 63;
-    auto launch = [&](auto kernel, int lds, auto c, auto big, auto ls) {
-        if (c == want_ch && big == want_big && ls == want_ls)
-            hipExtLaunchKernelGGL(kernel, dim3(rows / (256 / c)), dim3(512), lds, st, ev_start, ev_stop, 0, args);
-    };
-    if (act == Act::F16) for_each_tower64<_Float16>(launch);
-    else for_each_tower64<__bf16>(launch);
+    if (act == Act::F16) launch_tower64_of<_Float16>(args, rows, ch, layer_steps, st, ev_start, ev_stop);
+    else launch_tower64_of<__bf16>(args, rows, ch, layer_steps, st, ev_start, ev_stop);
+}
+
+void launch_tower64_stream(const Tower64Args& args, uint32_t rows, int ch, bool layer_steps, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
+    if (!(args.sat && args.out && !args.head_w)) {
+        fprintf(stderr, "cattus: launch_tower64_stream: needs Tower64Args::sat and ::out and no fused heads\n");
+        abort();
+    }
+    launch_tower64_of<Tower64Stream>(args, rows, ch, layer_steps, st, ev_start, ev_stop);
 }
 
 // The opt-in for > 64 KiB of dynamic LDS is a per-device function attribute.  Every instance of every family gets it here, once
@@ -2000,6 +2079,7 @@ hipError_t prepare_device() {
     conv_opt_in<ConvSplitW>(err);
     for_each_tower64<__bf16>([&](auto kernel, int lds, auto...) { lds_opt_in(err, kernel, lds); });
     for_each_tower64<_Float16>([&](auto kernel, int lds, auto...) { lds_opt_in(err, kernel, lds); });
+    for_each_tower64<Tower64Stream>([&](auto kernel, int lds, auto...) { lds_opt_in(err, kernel, lds); });
     for (hipError_t e : {prepare_tower64_split(), prepare_wino(), prepare_wino4(), prepare_winof4(), prepare_wino4s(), prepare_wino_f16(), prepare_wino_f32(), prepare_splitk()})
         if (err == hipSuccess) err = e;
     return err;

@@ -34,6 +34,10 @@ _DTYPES_WINO_F32 = {"f32w": DTYPE_F32W}
 # coverage).  A table of its own again: the two above stay what they were.
 DTYPE_F16R = 6
 _DTYPES_F16R = {"f16r": DTYPE_F16R}
+# "f16r_resident": dtype "f16r"'s arithmetic, bit for bit, as a demand for the one-launch LDS-resident form (CATTUS_DTYPE_F16R_RESIDENT: at most
+# 64 filters, where dtype "f16" accepts tower_form "resident").  A table of its own again: the three above stay what they were.
+DTYPE_F16R_RESIDENT = 7
+_DTYPES_F16R_RESIDENT = {"f16r_resident": DTYPE_F16R_RESIDENT}
 
 # every symbol include/cattus_hip.h declares
 ABI_SYMBOLS = [
@@ -346,6 +350,8 @@ class HipEvaluator:
         "f16r" (_DTYPES_F16R) is the direct single-term f16 tower with the residual stream kept in f32: dtype "f16"'s weights, shifts, calibration and coverage
         (any board, any filter count), one launch per layer, bits of its own; tower_form "resident" is refused, the other forms (forms of the "f16x2" tower) mean "auto"; calibrated, it keeps
         the BatchNorm estimate's shifts and takes only the headroom guard from the sample, as "f16w" does.
+        "f16r_resident" (_DTYPES_F16R_RESIDENT) is "f16r" in ONE LDS-resident launch (tower64_stream_kernel), the same bits: networks of at most 64 filters, where dtype "f16"
+        accepts tower_form "resident"; tower_form "auto" and "resident" both mean it, the forms of the "f16x2" tower are ignored, anything it does not cover is refused.
         tower_form: "auto" | "direct" | "winograd" | "winograd_f4" | "direct_splitk" (cattus_tower_form; None = "auto", or what CATTUS_WINOGRAD=0/1 in the
         environment says; "winograd_f4", the F(4x4,3x3) form, and "direct_splitk", the direct form with the K walk divided over a workgroup's waves
         for batches of a few leaves, are opt-in only: never what "auto" picks, and each has bits of its own; "resident" (TOWER_FORMS_RESIDENT)
@@ -375,7 +381,7 @@ class HipEvaluator:
         if switches is None:
             switches = {k: os.environ[k] for k in DIAG_SWITCHES if k in os.environ}
         self.tower_form = tower_form
-        cfg = EvalConfig(C.sizeof(EvalConfig), device, self.batch_size, self.plane_words, {**_DTYPES, **_DTYPES_WINO_F32, **_DTYPES_F16R}[dtype], flush_us, {**TOWER_FORMS, **TOWER_FORMS_RESIDENT}[tower_form], int(tail_leaves))
+        cfg = EvalConfig(C.sizeof(EvalConfig), device, self.batch_size, self.plane_words, {**_DTYPES_F16R_RESIDENT, **_DTYPES, **_DTYPES_WINO_F32, **_DTYPES_F16R}[dtype], flush_us, {**TOWER_FORMS, **TOWER_FORMS_RESIDENT}[tower_form], int(tail_leaves))
         h = C.c_void_p()
         buf = C.create_string_buffer(blob, len(blob))
         text = ";".join(f"{k}={v}" for k, v in switches.items()).encode() if switches else None

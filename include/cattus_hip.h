@@ -110,7 +110,7 @@ typedef enum cattus_dtype {
      * Coverage: every shape CATTUS_DTYPE_F16 runs on the MFMA per-layer tower -- any board up to 11x11, any filter count, up to 128
      * plane words, vhc + phc <= 32 (wider heads: CATTUS_E_UNSUPPORTED).  A SimpleTwoHeadedModel blob runs in f32, as under every dtype.
      * tower_form: AUTO means this tower; DIRECT, WINOGRAD, WINOGRAD_F4 and DIRECT_SPLITK, forms of the F16X2 tower, are ignored;
-     * RESIDENT is CATTUS_E_UNSUPPORTED (no resident kernel keeps an f32 stream: the follow-up).  tail_leaves is ignored
+     * RESIDENT is CATTUS_E_UNSUPPORTED (the one-launch form of this tower is CATTUS_DTYPE_F16R_RESIDENT, below).  tail_leaves is ignored
      * (cattus_hip_tail_leaves reports 0).  cattus_hip_time_tower reports 1 + 2 blocks launches.  Observation: the stream points (0,
      * 2i + 2) are tapped from S in f32, times 2^-t_k, the middle points from M.  The stream shifts are CATTUS_DTYPE_F16's (they protect the
      * f16 copy's small channels).  cattus_hip_create_calibrated is accepted as for CATTUS_DTYPE_F16, with CATTUS_DTYPE_F16W's rule, the
@@ -125,10 +125,40 @@ typedef enum cattus_dtype {
      * against float64 0.53x / 0.45x / 0.51x F16's on the chess 4x128 / chess 20x256 / hex7 6x64 fixtures (emulation, profiles/
      * gate_f16r.json: 0.53 / 0.44 / 0.52).  Search level (256 searches of 800 simulations on chess 20x256 against the f32 search): 100.0 %
      * of the moves equal, visit L1 mean 0.00006; F16 on the same searches 99.2 %, 0.00039, F16W 99.6 %, 0.00037.  RECOMMENDED wherever
-     * F16 or F16W is used today; not where a 64-filter resident form runs (F16X2's is 1.36x faster on hex7 6x64).  The estimate written
+     * F16 or F16W is used today; where a 64-filter resident form runs, as CATTUS_DTYPE_F16R_RESIDENT (below: the same bits in one launch).  The estimate written
      * before the run (+3 - 10 % on F16 by batch size) was met at its upper end.  Not measured: stamps, counters,
      * other filter counts than 256 / 128 / 64, batches below 64 leaves, two evaluators on one device. */
     CATTUS_DTYPE_F16R = 6,
+    /* CATTUS_DTYPE_F16R's arithmetic, BIT FOR BIT, as a demand for the ONE-LAUNCH LDS-RESIDENT form (K1hr resident,
+     * tower64_stream_kernel): every logit, every value and cattus_stats.saturated equal what the same blob returns from
+     * CATTUS_DTYPE_F16R, for every n, through every entry point (tests/test_f16r_resident_gpu.py).  Behaviour of CATTUS_DTYPE_F16R, of
+     * every other dtype and of every tower_form is unchanged; it is a dtype value because CATTUS_DTYPE_F16R with RESIDENT stays refused
+     * and this struct stays 32 bytes.  The launch is tower64_lds_kernel's f16 instantiation -- loader waves, weight ring, plane expansion,
+     * LDS plan (buffer 0 the f16 operand copy A, buffer 1 the planes and then the middle activation M) -- except where the stream lives:
+     * a consumer lane finishes the same output elements in every layer, so the f32 stream S of those elements stays in that lane's
+     * registers across the layer loop (16 values per lane at one board per workgroup, 32 at 128 rows) and never touches LDS; the last
+     * layer stores it as f32 rows and the two f32 head launches follow, as under CATTUS_DTYPE_F16 with RESIDENT.  Weights, [biases |
+     * inverse scales], stream shifts and cattus_hip_create_calibrated's rule are CATTUS_DTYPE_F16R's.
+     * Coverage: exactly the evaluators on which CATTUS_DTYPE_F16 accepts tower_form RESIDENT -- at most 64 (padded) filters, vhc + phc <=
+     * 32, at most 64 planes, no CATTUS_TOWER64=0; any board up to 11x11, any block count including 0 -- anything else is
+     * CATTUS_E_UNSUPPORTED (never other bits under this name).  A SimpleTwoHeadedModel blob runs in f32, as under every dtype.
+     * tower_form: AUTO and RESIDENT both mean this form; DIRECT, WINOGRAD, WINOGRAD_F4 and DIRECT_SPLITK are ignored as under
+     * CATTUS_DTYPE_F16R.  tail_leaves is ignored (cattus_hip_tail_leaves reports 0).  cattus_hip_time_tower reports 1 launch.
+     * Observation (cattus_hip_tap, cattus_hip_trace) runs the per-layer CATTUS_DTYPE_F16R pass on the same buffers: the same bits.
+     * MEASURED on one MI355X (scripts/f16r_resident_time.py -> profiles/f16r_resident.txt: one process, max_batch = n, five evaluators
+     * alternating over three rounds, 300 steps through cattus_hip_eval_device, min; F16R_RESIDENT | F16R | F16 RESIDENT | F16X2 | BF16, ms
+     * per step):
+     *   hex7 6x64:  32 leaves 0.042 | 0.072 | 0.040 | 0.053 | 0.024,  128: 0.043 | 0.075 | 0.041 | 0.053 | 0.025,  512: 0.059 | 0.110 | 0.058 | 0.088 | 0.037
+     *     (the tower: one launch of 25.8 / 26.3 / 42.7 us against 13 of 4.5 / 4.7 / 6.6 us);
+     *   chess 7x16: 64 leaves 0.050 | 0.083 | 0.049 | 0.061 | 0.031,  256: 0.053 | 0.094 | 0.052 | 0.062 | 0.032  (one launch of 32.4 / 33.5 us against 15 of 4.5 / 4.9).
+     * Against the 12 % by which two boxes differ on one binary: RECOMMENDED OVER CATTUS_DTYPE_F16R ON ALL FIVE SHAPES (40-47 % less time per
+     * step, the same bits); no shape was measured on which it is not.  It runs at F16 RESIDENT's speed (1.02-1.04x its step: inside that
+     * spread) at about half F16's per-leaf error, and takes 0.67-0.86x F16X2's step -- 14-33 % less, beyond the spread on every shape --
+     * at 11-bit operands where F16X2 has 22 bits; 1.6-1.7x BF16's step.  The estimate it was built on (DESIGN.md section 3, K1hr resident:
+     * about F16 RESIDENT's 0.041 ms at hex7 6x64 and 128 leaves, within 3 %) held for the step (0.0425) and was missed by a point on the
+     * margin (+3.7 % there, +2 - 4 % over the five shapes).  Not measured: in-kernel stamps or counters of tower64_stream_kernel, filter
+     * counts other than 64 and 16 (padded to 64), two evaluators sharing a device, self-play. */
+    CATTUS_DTYPE_F16R_RESIDENT = 7,
 } cattus_dtype;
 /* Every dtype takes any network the blob format and the plane pack allow: up to 128 plane words per leaf (planes x plane_words),
  * e.g. AlphaZero's 119 chess planes. */

@@ -23,6 +23,11 @@ pub enum HipDtype {
     F16x2 = 2,
     /// single-term f16 operands, f32 accumulation (throughput mode, 11 significant bits)
     F16 = 3,
+    /// (4 = f16w, 5 = f32w, 6 = f16r: opt-in towers of the C ABI and the Python self-player, not listed here)
+    /// f16 operands with the residual stream kept in f32, the whole tower in one LDS-resident launch: networks of at most 64 filters;
+    /// the bits of dtype f16r (`CATTUS_DTYPE_F16R_RESIDENT`), about half `F16`'s per-leaf error; refused where the form does not cover the network
+    #[serde(rename = "f16r_resident")]
+    F16rResident = 7,
 }
 
 #[repr(C)]
