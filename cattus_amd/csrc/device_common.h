@@ -226,6 +226,47 @@ __device__ __forceinline__ void finish_f16x2(const char* rowp, int px, int cg, c
     finish_f16x2_sums<CB, HAS_RES>(v, ds8, bias8, resv, valid, flags, sat, out, row, cout, col);
 }
 
+// ---- the value head's tanh (K5, the SIMT value kernels, the dense layers, the short-chain FC pair) ----
+// tanh from + - * / fmaf and exponent-bit edits only, so the CPU oracle reproduces it bit for bit.
+__device__ __forceinline__ float exp_pos(float x) {
+    const float log2e = 1.44269504088896341f;
+    const float ln2_hi = 0.693145751953125f;
+    const float ln2_lo = 1.42860682030941723e-06f;
+    const float nf = __builtin_rintf(x * log2e);
+    float rr = __builtin_fmaf(nf, -ln2_hi, x);
+    rr = __builtin_fmaf(nf, -ln2_lo, rr);
+    float p = 1.0f / 720.0f;
+    p = __builtin_fmaf(p, rr, 1.0f / 120.0f);
+    p = __builtin_fmaf(p, rr, 1.0f / 24.0f);
+    p = __builtin_fmaf(p, rr, 1.0f / 6.0f);
+    p = __builtin_fmaf(p, rr, 0.5f);
+    p = __builtin_fmaf(p, rr, 1.0f);
+    p = __builtin_fmaf(p, rr, 1.0f);
+    return __uint_as_float(__float_as_uint(p) + (((uint32_t)(int32_t)nf) << 23));
+}
+
+__device__ __forceinline__ float tanh_exact(float x) {
+    const float ax = __builtin_fabsf(x);
+    float t;
+    if (!(ax == ax)) return x;
+    if (ax < 0.5f) {
+        const float s = ax * ax;
+        float p = 21844.0f / 6081075.0f;
+        p = __builtin_fmaf(p, s, -1382.0f / 155925.0f);
+        p = __builtin_fmaf(p, s, 62.0f / 2835.0f);
+        p = __builtin_fmaf(p, s, -17.0f / 315.0f);
+        p = __builtin_fmaf(p, s, 2.0f / 15.0f);
+        p = __builtin_fmaf(p, s, -1.0f / 3.0f);
+        t = __builtin_fmaf(ax * s, p, ax);
+    } else if (ax < 10.0f) {
+        const float e = exp_pos(2.0f * ax);
+        t = 1.0f - 2.0f / (e + 1.0f);
+    } else {
+        t = 1.0f;
+    }
+    return x < 0.0f ? -t : t;
+}
+
 // ---- host side: a kernel family's instances, listed once ----
 // Next to its kernels every templated family has one for_each_* visitor.  It calls f(kernel, ..., template arguments as
 // std::integral_constant values) for every instance that exists; an `if constexpr` on the family's rule keeps the other

@@ -396,6 +396,11 @@ struct cattus_eval {
     // leaves runs the layers behind the stem on the small-tile kernel (kernels_wino4s.hip), the same bits; tail_batches counts those passes
     uint32_t tail_leaves = 0;
     std::atomic<uint64_t> tail_batches{0};
+    // cattus_hip_head_chain as it holds (0 wherever the heads are not the f32 MFMA heads): an unobserved, untimed pass of at most this many leaves runs
+    // FC1 + FC2 and the policy FC on head_fc_chain_kernel (kernels_head_chain.hip) instead of head_fc_pair_kernel<float>, the same bits;
+    // head_chain_batches counts those passes.  Written with every lane mutex held, read by a pass under its lane's
+    std::atomic<uint32_t> head_chain{0};
+    std::atomic<uint64_t> head_chain_batches{0};
     int splitk_forced = 0;  // CATTUS_SPLITK_WAYS=1|2|4|8: the way count of the split-K direct form (tests and A/B; 0: splitk_rule.h's rule)
     // the f16 towers carry the residual stream at 2^stream_shift times its size, channel k of it at 2^stream_shifts[k] >= that
     // (choose_stream_shift; from cattus_hip_create_calibrated: calibrated_stream_shifts, whose headroom guard can take a channel
@@ -1007,7 +1012,13 @@ struct Forward {
         hd.hw = e->hw, hd.vhc = d.vhc, hd.phc = d.phc, hd.kvp = e->kvp, hd.kpp = e->kpp, hd.M = d.moves;
         hd.w2 = e->w2.as<float>(), hd.b2 = e->b2.as<float>(), hd.value = d_value;
         hd.slots = e->slots, hd.hv_leaves = hv_leaves(e);
-        launch_heads_mfma(head_act(e->act), tower, n, FP, hd, st);
+        const uint32_t chain_leaves = e->head_chain.load(std::memory_order_relaxed);
+        if (!obs && !tt && chain_leaves && n <= chain_leaves) {  // the short-chain form of the f32 FC pair (head_chain_rule.h): the same bits
+            e->head_chain_batches.fetch_add(1, std::memory_order_relaxed);
+            launch_heads_chain(head_act(e->act), tower, n, FP, hd, st);
+        } else {
+            launch_heads_mfma(head_act(e->act), tower, n, FP, hd, st);
+        }
         seen(net_points(d) - 1, L.hv.p, head_source());
     }
 
@@ -1393,6 +1404,32 @@ CATTUS_API int cattus_hip_splitk_plan(const cattus_eval* e, uint32_t* ways, uint
 CATTUS_API int cattus_hip_tail_batches(cattus_eval* e, uint64_t* batches) {
     if (!e || !batches) return fail(CATTUS_E_INVALID, "NULL argument");
     *batches = e->tail_batches.load(std::memory_order_relaxed);
+    return CATTUS_OK;
+}
+
+// the f32 MFMA heads: a tuned tower (Forward::heads_mfma) whose head kernels run in f32, within what one workgroup of the chain form keeps in LDS
+static bool heads_are_f32_mfma(const cattus_eval* e) {
+    return e->plan.tuned() && head_act(e->act) == Act::F32 && hc_lds_bytes(2, e->kvp, e->kpp) <= HC_LDS_MAX;
+}
+
+CATTUS_API int cattus_hip_head_chain(cattus_eval* e, uint32_t leaves) {
+    if (!e) return fail(CATTUS_E_INVALID, "NULL argument");
+    if (leaves > e->cfg.max_batch) return fail(CATTUS_E_INVALID, "head_chain: %u leaves is more than max_batch %u", leaves, e->cfg.max_batch);
+    std::unique_lock<std::mutex> held[NLANES];  // every lane, in lane order: batches in flight finish first, none starts meanwhile
+    for (int i = 0; i < NLANES; i++) held[i] = std::unique_lock<std::mutex>(e->lanes[i].mu);
+    e->head_chain = heads_are_f32_mfma(e) ? leaves : 0;
+    return CATTUS_OK;
+}
+
+CATTUS_API int cattus_hip_head_chain_leaves(const cattus_eval* e, uint32_t* effective) {
+    if (!e || !effective) return fail(CATTUS_E_INVALID, "NULL argument");
+    *effective = e->head_chain.load(std::memory_order_relaxed);
+    return CATTUS_OK;
+}
+
+CATTUS_API int cattus_hip_head_chain_batches(cattus_eval* e, uint64_t* batches) {
+    if (!e || !batches) return fail(CATTUS_E_INVALID, "NULL argument");
+    *batches = e->head_chain_batches.load(std::memory_order_relaxed);
     return CATTUS_OK;
 }
 

@@ -11,6 +11,7 @@
 #include "winof4_rule.h"  // the Winograd F(4x4, 3x3) form: matrices, transforms, geometry, cap, U index
 #include "splitk_rule.h"  // the split-K direct form: ways, ranges, reduction order, grid map, LDS plan
 #include "f16r_rule.h"    // dtype f16r: the epilogue with an f32 residual stream, the lane buffers' roles, the tap layout per point
+#include "head_chain_rule.h"  // the short-chain form of the f32 FC pair: grid map, operand offsets, walk order, epilogues
 #include "t64r_rule.h"    // dtype f16r_resident: that tower in one LDS-resident launch -- who owns an element, the LDS buffers, the layer table
 
 namespace cattus {
@@ -320,6 +321,13 @@ struct HeadsMfma {
     uint32_t slots;  // pixel slots per board of the tower (tower_slots)
 };
 void launch_heads_mfma(Act act, const void* tower, uint32_t nb, uint32_t F, const HeadsMfma& hd, hipStream_t st);
+// K4c + K5c (kernels_head_chain.hip; head_chain_rule.h has the rule): launch_heads_mfma for Act::F32 with the FC pair on head_fc_chain_kernel -- one
+// lane per output element (two of two leaves beyond HC_SINGLE_MAX leaves), a v_fma_f32 chain in the MFMA's k order instead of the MFMA chain: THE SAME
+// BITS in policy and value.  Same operands, same hv (written by the same head conv launch, or by a resident tower when tower == nullptr), nothing
+// uploaded twice.  Act::BF16 aborts: the bf16 pair has no such chain.
+void launch_heads_chain(Act act, const void* tower, uint32_t nb, uint32_t F, const HeadsMfma& hd, hipStream_t st);
+// the head conv launch of launch_heads_mfma alone (K3; kernels.hip)
+void launch_heads_conv(Act act, const void* tower, uint32_t nb, uint32_t F, const HeadsMfma& hd, hipStream_t st);
 
 // ---- K3-K5: heads, SIMT f32 (generic tower layout), same term order as the MFMA path ------
 // Tower output addressing: element (b, k, p) at  x[b*sb + k*sk + p*sp]  (elements of type `act`).

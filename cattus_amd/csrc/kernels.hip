@@ -2134,6 +2134,13 @@ void launch_conv3x3_generic(const float* in, const float* w, const float* bias, 
 // group -- the order an MFMA lane pair (k = 4h + j) produces -- in the MFMA kernels, in the SIMT
 // kernels of the generic path, and in the CPU oracle alike.
 __host__ __device__ constexpr uint32_t kperm(uint32_t kk) { return (kk & ~7u) + ((kk & 1u) << 2) + ((kk & 7u) >> 1); }
+// the short-chain form of the FC pair (head_chain_rule.h, kernels_head_chain.hip) walks the same order
+constexpr bool hc_order_is_kperm() {
+    for (uint32_t t = 0; t < 4096; t++)
+        if (hc_term_k(t) != kperm(t)) return false;
+    return true;
+}
+static_assert(hc_order_is_kperm(), "head_chain_rule.h's order is kperm");
 
 // ---- MFMA path: D[i][j] = sum_k P[i][k] * Q[j][k], K contiguous in both operands ------------
 enum { EPI_FC1 = 1, EPI_POLICY = 2 };
@@ -2338,7 +2345,6 @@ struct HeadFcTail {
     const float *w2, *b2;
     float* value;
 };
-__device__ __forceinline__ float tanh_exact(float x);
 template <typename T>
 __global__ void __launch_bounds__(256) head_fc_pair_kernel(const T* __restrict__ p1, const T* __restrict__ q1,
                                                            const T* __restrict__ p2, const T* __restrict__ q2, uint32_t I,
@@ -2377,15 +2383,24 @@ static void launch_head_conv(Act act, const void* P, uint32_t ldp, uint32_t I, c
         hipLaunchKernelGGL(head_conv_kernel<float>, grid, block, 0, st, (const float*)P, ldp, I, (const float*)Q, ldq, J, K, ep);
 }
 
-void launch_heads_mfma(Act act, const void* tower, uint32_t nb, uint32_t F, const HeadsMfma& hd, hipStream_t st) {
+static HeadEpi heads_epi(const HeadsMfma& hd) {
     HeadEpi ep{};
     ep.hw = hd.hw, ep.vhc = hd.vhc, ep.ocn = hd.vhc + hd.phc, ep.kvp = hd.kvp, ep.kpp = hd.kpp, ep.M = hd.M;
     ep.hv_pol = hd.hv_leaves * hd.kvp;
     ep.slots = hd.slots;
-    // K3: both 1x1 convs in one GEMM: i = head channel, j = tower row (tower == nullptr: hv was already written
-    // by the resident tower kernel, which fuses this step); writes hv in fragment order
     ep.bias = hd.conv_b, ep.out = hd.hv;
-    if (tower) launch_head_conv(act, hd.conv_w, F, 32, tower, F, nb * hd.slots, F, ep, st);
+    return ep;
+}
+
+// K3: both 1x1 convs in one GEMM: i = head channel, j = tower row (tower == nullptr: hv was already written
+// by the resident tower kernel, which fuses this step); writes hv in fragment order
+void launch_heads_conv(Act act, const void* tower, uint32_t nb, uint32_t F, const HeadsMfma& hd, hipStream_t st) {
+    if (tower) launch_head_conv(act, hd.conv_w, F, 32, tower, F, nb * hd.slots, F, heads_epi(hd), st);
+}
+
+void launch_heads_mfma(Act act, const void* tower, uint32_t nb, uint32_t F, const HeadsMfma& hd, hipStream_t st) {
+    const HeadEpi ep = heads_epi(hd);
+    launch_heads_conv(act, tower, nb, F, hd, st);
     // K4 + K5 in one launch: value FC1 (+ReLU): i = leaf, j = hidden unit; policy FC: i = leaf, j = move
     const size_t esz = act == Act::BF16 ? 2 : 4;
     if (!nb) return;
@@ -2458,46 +2473,7 @@ void launch_value_fc1(const float* hv, uint32_t hv_stride, const float* w1t, con
     hipLaunchKernelGGL(value_fc1_kernel, dim3(b), dim3(128), 0, st, hv, hv_stride, w1t, b1, K, h1);
 }
 
-// tanh from + - * / fmaf and exponent-bit edits only, so the CPU oracle reproduces it bit for bit.
-__device__ __forceinline__ float exp_pos(float x) {
-    const float log2e = 1.44269504088896341f;
-    const float ln2_hi = 0.693145751953125f;
-    const float ln2_lo = 1.42860682030941723e-06f;
-    const float nf = __builtin_rintf(x * log2e);
-    float rr = __builtin_fmaf(nf, -ln2_hi, x);
-    rr = __builtin_fmaf(nf, -ln2_lo, rr);
-    float p = 1.0f / 720.0f;
-    p = __builtin_fmaf(p, rr, 1.0f / 120.0f);
-    p = __builtin_fmaf(p, rr, 1.0f / 24.0f);
-    p = __builtin_fmaf(p, rr, 1.0f / 6.0f);
-    p = __builtin_fmaf(p, rr, 0.5f);
-    p = __builtin_fmaf(p, rr, 1.0f);
-    p = __builtin_fmaf(p, rr, 1.0f);
-    return __uint_as_float(__float_as_uint(p) + (((uint32_t)(int32_t)nf) << 23));
-}
-
-__device__ __forceinline__ float tanh_exact(float x) {
-    const float ax = __builtin_fabsf(x);
-    float t;
-    if (!(ax == ax)) return x;
-    if (ax < 0.5f) {
-        const float s = ax * ax;
-        float p = 21844.0f / 6081075.0f;
-        p = __builtin_fmaf(p, s, -1382.0f / 155925.0f);
-        p = __builtin_fmaf(p, s, 62.0f / 2835.0f);
-        p = __builtin_fmaf(p, s, -17.0f / 315.0f);
-        p = __builtin_fmaf(p, s, 2.0f / 15.0f);
-        p = __builtin_fmaf(p, s, -1.0f / 3.0f);
-        t = __builtin_fmaf(ax * s, p, ax);
-    } else if (ax < 10.0f) {
-        const float e = exp_pos(2.0f * ax);
-        t = 1.0f - 2.0f / (e + 1.0f);
-    } else {
-        t = 1.0f;
-    }
-    return x < 0.0f ? -t : t;
-}
-
+// (exp_pos and tanh_exact: device_common.h, shared with kernels_head_chain.hip)
 __global__ void __launch_bounds__(256) value_fc2_tanh_kernel(const float* __restrict__ h1, const float* __restrict__ w2,
                                                              const float* __restrict__ b2, uint32_t nb,
                                                              float* __restrict__ value) {

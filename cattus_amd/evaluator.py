@@ -69,6 +69,9 @@ ABI_SYMBOLS = [
     "cattus_hip_tower_kernel",
     "cattus_hip_tail_leaves",
     "cattus_hip_tail_batches",
+    "cattus_hip_head_chain",
+    "cattus_hip_head_chain_leaves",
+    "cattus_hip_head_chain_batches",
     "cattus_hip_stream_range",
     "cattus_hip_create_calibrated",
     "cattus_hip_verify",
@@ -245,6 +248,9 @@ def load_library():
     L.cattus_hip_tower_kernel.restype = C.c_char_p
     L.cattus_hip_tail_leaves.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.cattus_hip_tail_batches.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.cattus_hip_head_chain.argtypes = [vp, C.c_uint32]
+    L.cattus_hip_head_chain_leaves.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.cattus_hip_head_chain_batches.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.cattus_hip_stream_shift.argtypes = [vp]
     L.cattus_hip_stream_shifts.argtypes = [vp, C.POINTER(C.c_int), C.c_uint32]
     L.cattus_hip_stem_input.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -342,6 +348,7 @@ class HipEvaluator:
         calibration=None,
         verify_every: int = 0,
         tail_leaves: int = 0,
+        head_chain_leaves: int = 0,
     ):
         """dtype: "f32" | "bf16" | "f16x2" | "f16" | "f16w" | "f32w" (cattus_dtype).  "f16w" is the single-term f16 tower in Winograd F(2x2,3x3) form with an f32 stream: an 8x8
         board, at least one residual block, a multiple of 64 filters >= 128, tower_form "auto" or "winograd" (both mean it); anything else is refused.
@@ -363,7 +370,9 @@ class HipEvaluator:
         BatchNorm estimate's shifts and takes only the headroom guard from the sample).  verify_every: N >= 1
         checks every Nth batch against a shadow f32 tower (``verify``); 0, the default, builds no shadow and checks nothing.
         tail_leaves: k >= 1 runs batches of at most k leaves of the Winograd F(2x2,3x3) tower on its small-tile kernel (cattus_eval_config.tail_leaves:
-        the same bits, more workgroups for a short batch); ignored on every other plan (``tail_leaves()`` says what holds); 0, the default: off."""
+        the same bits, more workgroups for a short batch); ignored on every other plan (``tail_leaves()`` says what holds); 0, the default: off.
+        head_chain_leaves: k >= 1 runs the f32 heads' FC pair of batches of at most k leaves as short fmaf chains (``head_chain``: the same bits);
+        ignored where the heads are not the f32 MFMA heads (``head_chain_leaves()`` says what holds); 0, the default: off."""
         self.desc: NetDesc = parse_header(blob)
         self.batch_size = int(batch_size)
         self.plane_words = int(plane_words)
@@ -397,12 +406,14 @@ class HipEvaluator:
             _check(self._lib.cattus_hip_create(buf, len(blob), C.byref(cfg), C.byref(h)))
         self._h = h
         self._blob = blob  # cattus_hip_verify takes it again: the library keeps no host copy
-        if verify_every:
-            try:
+        try:
+            if head_chain_leaves:
+                self.head_chain(head_chain_leaves)
+            if verify_every:
                 self.verify(verify_every)
-            except Exception:
-                self.close()
-                raise
+        except Exception:
+            self.close()
+            raise
 
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):
@@ -684,6 +695,24 @@ class HipEvaluator:
         k = C.c_uint32()
         _check(self._lib.cattus_hip_tail_leaves(self._h, C.byref(k)))
         return k.value
+
+    def head_chain(self, leaves: int) -> None:
+        """``cattus_hip_head_chain``: batches of at most ``leaves`` leaves run value FC1 + FC2 and the policy FC on head_fc_chain_kernel (one output element
+        per lane, an fmaf chain in the MFMA's order: the same bits); 0: the MFMA pair for every batch, the default.  More than ``batch_size`` is refused;
+        accepted and ignored where the heads are not the f32 MFMA heads ("bf16", more than 32 head channels, a SimpleTwoHeadedModel)."""
+        _check(self._lib.cattus_hip_head_chain(self._h, int(leaves)))
+
+    def head_chain_leaves(self) -> int:
+        """The ``head_chain`` setting as it holds for this evaluator: 0 where it is off or ignored."""
+        k = C.c_uint32()
+        _check(self._lib.cattus_hip_head_chain_leaves(self._h, C.byref(k)))
+        return int(k.value)
+
+    def head_chain_batches(self) -> int:
+        """Batches whose FC pair took the chain form since the evaluator was created."""
+        k = C.c_uint64()
+        _check(self._lib.cattus_hip_head_chain_batches(self._h, C.byref(k)))
+        return int(k.value)
 
     def tail_batches(self) -> int:
         """Batches that took the short path (at most ``tail_leaves()`` leaves) since the evaluator was created."""

@@ -638,6 +638,8 @@ def main(argv=None):
     # optional: batches of at most this many leaves on the Winograd tower's small-tile kernel (cattus_eval_config.tail_leaves: the same bits);
     # absent or 0: off
     tail_leaves = int(inf.get("tail_leaves", 0))
+    # optional: the f32 heads' FC pair of batches of at most this many leaves as short fmaf chains (cattus_hip_head_chain: the same bits); absent or 0: off
+    head_chain_leaves = int(inf.get("head_chain_leaves", 0))
     # optional: the form of the f16x2 tower (cattus_tower_form): "auto" (absent), "direct", "winograd", "winograd_f4", or "direct_splitk" -- the
     # direct form for batches of a few leaves, the reference's threads: 8, batch_size: 1 (include/cattus_hip.h); or "resident": the one-launch
     # LDS-resident tower of a network with at most 64 filters, for dtype f16 the only way to it
@@ -646,7 +648,7 @@ def main(argv=None):
     def load(path):
         blob = Path(path).read_bytes()
         return HipEvaluator(blob, batch_size=engine["model"]["batch_size"], plane_words=info["plane_words"],
-                            dtype=inf.get("dtype", "f16x2"), device=inf.get("device", 0), verify_every=verify_every, tail_leaves=tail_leaves,
+                            dtype=inf.get("dtype", "f16x2"), device=inf.get("device", 0), verify_every=verify_every, tail_leaves=tail_leaves, head_chain_leaves=head_chain_leaves,
                             tower_form=tower_form)
 
     ev1 = load(args.model1_path)

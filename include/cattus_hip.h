@@ -555,6 +555,28 @@ int cattus_hip_tail_leaves(const cattus_eval* e, uint32_t* effective);
  * point; a timing pass of cattus_hip_time_tower is not a batch. */
 int cattus_hip_tail_batches(cattus_eval* e, uint64_t* batches);
 
+/* The f32 heads' FC pair as short chains.  0 (the default): nothing changes.  k >= 1: a batch of n <= k leaves runs FC1 + FC2 and the policy FC on
+ * head_fc_chain_kernel instead of head_fc_pair_kernel<float>: one output element per lane, its dot product a v_fma_f32 chain in the MFMA's k order
+ * (4 cycles per k where the pair's single v_mfma_f32_32x32x2_f32 chain pays 32) on the operands the heads already have -- no second upload, no new
+ * layout; the head convs are untouched.  THE BITS DO NOT CHANGE: every logit, value and prior equals what the evaluator returns with 0, for every n
+ * and k, through every entry point (tests/test_head_chain_gpu.py).  k > max_batch: CATTUS_E_INVALID.  Accepted and ignored
+ * (cattus_hip_head_chain_leaves reports 0) where the heads are not the f32 MFMA heads: dtype bf16, value + policy head channels > 32 (generic
+ * path), SimpleTwoHeadedModel.  Waits for the batches in flight.  Observed passes (tap, trace), cattus_hip_time_tower, the verification shadow and
+ * the calibration's temporary evaluator keep the MFMA pair.
+ * Measured (whole step through cattus_hip_eval_device, ms, 0 | k = n, one evaluator alternating, min of 3 rounds x 300 steps; scripts/head_chain_time.py ->
+ * profiles/head_chain.txt): hex7 6x64 f16x2  32 leaves 0.0612 | 0.0595, 128: 0.0616 | 0.0599, 512: 0.0969 | 0.0978;  f16r_resident  32: 0.0499 | 0.0484,
+ * 128: 0.0506 | 0.0496, 512: 0.0678 | 0.0708;  f32  128: 0.1796 | 0.1786.  chess 7x16 f16x2  1: 0.0586 | 0.0551, 8: 0.0590 | 0.0557, 64: 0.0603 | 0.0597,
+ * 256: 0.0618 | 0.0754;  f16r_resident  1: 0.0472 | 0.0437, 8: 0.0488 | 0.0455, 64: 0.0500 | 0.0496, 256: 0.0530 | 0.0661.  chess 20x256 f16x2: within
+ * 1.2 % either way at 1 .. 256.  The estimate this was built on (the FC launch 12-18 -> 4-7 us on K = 784, the hex7 step -15 to -20 %) WAS MISSED: the
+ * step falls by 2-3 % on hex7 6x64 and by 6-7 % on chess 7x16 up to 8 leaves, and from the batch whose grid passes one workgroup per CU on it RISES
+ * (chess, 1880 moves: +22-25 % at 256 leaves).  No shape reaches the 12 % by which two boxes differ on one binary, so the chain form is RECOMMENDED
+ * NOWHERE; where it is tried, never set k above 64 on a chess head (1880 moves) or 128 on a hex7 head (49 moves).  The default stays 0.  Not measured:
+ * the FC launch alone (no kernel trace of the new build), self-play throughput, boards other than 7x7 and 8x8, more than 512 leaves. */
+int cattus_hip_head_chain(cattus_eval* e, uint32_t leaves);
+int cattus_hip_head_chain_leaves(const cattus_eval* e, uint32_t* effective);
+/* Batches whose FC pair took the chain form since the evaluator was created, through any entry point (as cattus_hip_tail_batches). */
+int cattus_hip_head_chain_batches(cattus_eval* e, uint64_t* batches);
+
 const char* cattus_hip_last_error(void);
 const char* cattus_hip_version(void);
 /* What the last cattus_hip_create found for HIP_FORCE_DEV_KERNARG (the host process exports it before HIP initialises:
