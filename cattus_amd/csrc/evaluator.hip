@@ -356,6 +356,10 @@ enum class TowerKind {
     // in one LDS-resident launch (K1hr resident: tower64_stream_kernel; t64r_rule.h) -- the f32 stream in the owning lanes' registers, dtype
     // f16r's weights, scales, shifts, calibration and bits; Resident64's coverage, workgroup shapes and switches; observed on PerLayerStream
     Resident64Stream,
+    // dtype f32_resident (Act::F32 with this kind, and no other kind for that dtype): PerLayer's exact f32 tower of a network with <= 64 filters
+    // and <= 32 planes in one LDS-resident launch (K1rf: tower64_f32_kernel; t64f_rule.h) -- dtype f32's weights, biases and bits; the resident
+    // predicate's coverage with a one-chunk stem; observed on PerLayer; like dtype f32 it is the exact tower and has no shadow
+    Resident64F32,
 };
 struct TowerPlan {
     TowerKind kind = TowerKind::Generic;
@@ -365,7 +369,7 @@ struct TowerPlan {
     // a layer has more tiles than the device has CUs (CATTUS_WINO_PERSIST=0: per-layer launches) -- for the batches one_launch_now() admits
     bool one_launch = false;
     bool tuned() const { return kind != TowerKind::Simple && kind != TowerKind::Generic; }  // the MFMA NHWC towers
-    bool resident() const { return kind == TowerKind::Resident64 || kind == TowerKind::Resident64Split || kind == TowerKind::Resident64Stream; }  // one launch, activations in LDS
+    bool resident() const { return kind == TowerKind::Resident64 || kind == TowerKind::Resident64Split || kind == TowerKind::Resident64Stream || kind == TowerKind::Resident64F32; }  // one launch, activations in LDS
     bool f32_stream() const { return kind == TowerKind::PerLayerStream || kind == TowerKind::Resident64Stream; }  // dtype f16r's arithmetic (f16r_rule.h)
     bool wino() const { return kind == TowerKind::Wino16 || kind == TowerKind::Wino4 || kind == TowerKind::WinoF4 || kind == TowerKind::WinoF16 || kind == TowerKind::WinoF32; }  // f32 rows between the layers
 };
@@ -388,6 +392,7 @@ struct cattus_eval {
     int t64s_depth = 0;           // CATTUS_T64S_SHAPE=1|2: workgroup shape of the resident split tower (kernels.h; 0: by grid size)
     bool pack_separately = false;  // more than 32 planes, or CATTUS_FUSED_STEM=0 (A/B, tests): the plane pack as its own launch in front of the stem
     int t64_force_ch = 0;          // CATTUS_T64_CH=2|4: workgroup shape of the resident tower (A/B runs, the row-split test)
+    bool t64f_narrow = true;       // CATTUS_T64F_NARROW=0: the resident f32 tower walks both chunks of a <= 32-filter network too (A/B, the equality test)
     // the one-launch Winograd tower: set when a launch reported a hand-off wait that gave up (CATTUS_WINO_SPIN=<polls>: the budget of a
     // wait) -- that batch is run again on the per-layer launches, and so is every later one
     std::atomic<bool> tower_gave_up{false};
@@ -711,6 +716,14 @@ int build(cattus_eval* e, const float* p, const Calibration* cal) {
         }
         if ((rc = e->t64_layers.upload(tl.data(), tl.size() * sizeof(Tower64Layer)))) return rc;
     }
+    if (plan.kind == TowerKind::Resident64F32) {  // t64f_rule.h's table: dtype f32's rows and biases, the skip flag per layer
+        std::vector<Tower64Layer> tl;
+        for (uint32_t l = 0; l < t64f_layers(d.blocks); l++) {
+            const ConvLayer& c = l == 0 ? e->stem : (l & 1) ? *e->c1[(l - 1) / 2] : *e->c2[(l - 1) / 2];
+            tl.push_back(Tower64Layer{c.w.p, c.b.as<float>(), t64f_layer(l, d.blocks).skip ? 1 : 0, 0});
+        }
+        if ((rc = e->t64_layers.upload(tl.data(), tl.size() * sizeof(Tower64Layer)))) return rc;
+    }
     if (plan.kind == TowerKind::Resident64Split) {
         const auto tl = layer_table([](const ConvLayer& c, int res, bool stem) { return Tower64SplitLayer{c.w.p, c.b.as<float>(), res, stem ? 1 : 2}; });
         if ((rc = e->t64_layers.upload(tl.data(), tl.size() * sizeof(Tower64SplitLayer)))) return rc;
@@ -884,6 +897,18 @@ struct Forward {
         return ta.out;
     }
 
+    // dtype f32_resident: the tower's output as the plain f32 rows the per-layer f32 tower leaves, in `a`, for the f32 head kernels
+    const void* resident64_f32() {
+        Tower64F32Args ta{};
+        ta.planes = d_planes, ta.layers = e->t64_layers.as<Tower64Layer>(), ta.out = a;
+        ta.n = n, ta.C = d.planes, ta.w64 = w64, ta.S = S, ta.nlayers = t64f_layers(d.blocks);
+        ta.nch = (uint32_t)t64f_hidden_chunks(F, e->t64f_narrow);
+        const uint32_t rows = nb * e->slots;
+        hipEvent_t s0 = ev(), s1 = ev();
+        launch_tower64_f32(ta, rows, t64f_ch(rows / e->slots, e->slots, e->t64_force_ch), st, s0, s1);
+        return ta.out;
+    }
+
     // CATTUS_T64S_HEADS=0: the tower's output as plain f32 rows in `a` for the f32 head kernels
     const void* resident64_split() {
         Tower64SplitArgs ta{};
@@ -1053,6 +1078,7 @@ int enqueue_forward(cattus_eval* e, Lane& L, const uint64_t* d_planes, uint32_t 
         case TowerKind::Resident64: f.heads_mfma(f.resident64()); break;
         case TowerKind::Resident64Split: f.heads_mfma(f.resident64_split()); break;
         case TowerKind::Resident64Stream: f.heads_mfma(f.resident64_stream()); break;
+        case TowerKind::Resident64F32: f.heads_mfma(f.resident64_f32()); break;
         case TowerKind::Wino16:
         case TowerKind::Wino4:
         case TowerKind::WinoF4:
@@ -1374,6 +1400,7 @@ CATTUS_API const char* cattus_hip_tower_kernel(const cattus_eval* e) {
         case TowerKind::Resident64: return "tower64_lds_kernel";
         case TowerKind::Resident64Split: return "tower64_split_kernel";
         case TowerKind::Resident64Stream: return "tower64_stream_kernel";
+        case TowerKind::Resident64F32: return "tower64_f32_kernel";
         case TowerKind::Wino16: return "conv3x3_wino_kernel";
         case TowerKind::Wino4: return one_launch_now(e, e->bpad) ? "tower_wino4_kernel" : "conv3x3_wino4_kernel";
         case TowerKind::WinoF4: return "conv3x3_winof4_kernel";
@@ -1460,7 +1487,7 @@ struct Switches {
         if (!text) return CATTUS_OK;
         static const char* const known[] = {"CATTUS_CONV_CB", "CATTUS_CONV_PBW", "CATTUS_FUSED_STEM", "CATTUS_T64_CH", "CATTUS_T64_LS", "CATTUS_SPLIT_W",
                                             "CATTUS_T64S_HEADS", "CATTUS_T64S_SHAPE", "CATTUS_TOWER64", "CATTUS_FORCE_GENERIC", "CATTUS_WINO_INPLACE",
-                                            "CATTUS_ARENA", "CATTUS_WINO_KERNEL", "CATTUS_WINO_PERSIST", "CATTUS_WINO_SPIN", "CATTUS_STREAM_SHIFT", "CATTUS_SPLITK_WAYS"};
+                                            "CATTUS_ARENA", "CATTUS_WINO_KERNEL", "CATTUS_WINO_PERSIST", "CATTUS_WINO_SPIN", "CATTUS_STREAM_SHIFT", "CATTUS_SPLITK_WAYS", "CATTUS_T64F_NARROW"};
         const std::string s(text);
         size_t at = 0;
         while (at < s.size()) {
@@ -1547,6 +1574,17 @@ int resolve_plan(const cattus_net_desc& d, const cattus_eval_config& cfg, const 
         plan->kind = TowerKind::Resident64Stream;
         return CATTUS_OK;
     }
+    // dtype f32_resident: dtype f32's arithmetic, bit for bit, as a demand for the one-launch LDS-resident form and nothing else -- wherever the
+    // resident predicate above holds and the stem's input is one 128-byte chunk of f32 (at most 32 planes); AUTO and RESIDENT both mean it, the
+    // forms 1-4 are ignored as under f32, tail_leaves is ignored; anything the form does not cover is refused, never other bits under this name
+    if (cfg.dtype == CATTUS_DTYPE_F32_RESIDENT && !simple) {
+        if (!(resident && cpad0 == 32))
+            return fail(CATTUS_E_UNSUPPORTED, "dtype f32_resident is dtype f32 in the one-launch LDS-resident form: at most 64 filters, at most 32 planes, value + policy head channels <= 32 "
+                                              "(and no CATTUS_TOWER64=0); dtype f32 runs every other shape per layer");
+        *plan = TowerPlan();
+        plan->kind = TowerKind::Resident64F32;
+        return CATTUS_OK;
+    }
     // the 4-frequency kernel wherever it covers the layer shape (filters a multiple of 64), else the 16-frequency one (128)
     const char* wk = sw.get("CATTUS_WINO_KERNEL");
     if (wk && strcmp(wk, "k16") != 0 && strcmp(wk, "k4") != 0) return fail(CATTUS_E_INVALID, "CATTUS_WINO_KERNEL is k16 or k4");
@@ -1628,7 +1666,8 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
         return fail(CATTUS_E_INVALID, "plane_words %u cannot hold a %ux%u board", cfg->plane_words, d.board, d.board);
     if (d.planes * cfg->plane_words > 128) return fail(CATTUS_E_UNSUPPORTED, "more than 128 plane words per leaf");
     if (cfg->dtype != CATTUS_DTYPE_F32 && cfg->dtype != CATTUS_DTYPE_BF16 && cfg->dtype != CATTUS_DTYPE_F16X2 && cfg->dtype != CATTUS_DTYPE_F16 &&
-        cfg->dtype != CATTUS_DTYPE_F16W && cfg->dtype != CATTUS_DTYPE_F32W && cfg->dtype != CATTUS_DTYPE_F16R && cfg->dtype != CATTUS_DTYPE_F16R_RESIDENT)
+        cfg->dtype != CATTUS_DTYPE_F16W && cfg->dtype != CATTUS_DTYPE_F32W && cfg->dtype != CATTUS_DTYPE_F16R && cfg->dtype != CATTUS_DTYPE_F16R_RESIDENT &&
+        cfg->dtype != CATTUS_DTYPE_F32_RESIDENT)  // (8 is unassigned)
         return fail(CATTUS_E_INVALID, "unknown dtype %u", cfg->dtype);
     if (!simple && (size_t)d.phc * d.board * d.board * 8 * 4 > 64 * 1024) return fail(CATTUS_E_UNSUPPORTED, "policy head too wide for the FC kernel");
 
@@ -1670,6 +1709,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
     e->wait_spin = !(wait_mode && strcmp(wait_mode, "block") == 0);
     e->pack_separately = d.planes > 32 || sw.starts("CATTUS_FUSED_STEM", '0');
     e->t64_force_ch = sw.number("CATTUS_T64_CH");
+    e->t64f_narrow = !sw.starts("CATTUS_T64F_NARROW", '0');
     e->t64_layer_steps = !(sw.get("CATTUS_T64_LS") && sw.number("CATTUS_T64_LS") == 0);
     e->stream_shift_on = !sw.starts("CATTUS_STREAM_SHIFT", '0');
     e->t64s_fuse_heads = !sw.starts("CATTUS_T64S_HEADS", '0');
@@ -1682,7 +1722,7 @@ int create_impl(const void* weights, size_t nbytes, const cattus_eval_config* cf
              : cfg->dtype == CATTUS_DTYPE_BF16 ? Act::BF16
              : cfg->dtype == CATTUS_DTYPE_F16X2 ? Act::F16S
              : cfg->dtype == CATTUS_DTYPE_F16 || cfg->dtype == CATTUS_DTYPE_F16W || cfg->dtype == CATTUS_DTYPE_F16R || cfg->dtype == CATTUS_DTYPE_F16R_RESIDENT ? Act::F16  // f16w: the direct f16 stem, f16r / f16r_resident: f16 operands; resolve_plan chooses their towers
-                                              : Act::F32;  // f32w too: the direct f32 stem and f32 rows; resolve_plan chooses its tower
+                                              : Act::F32;  // f32w and f32_resident too: dtype f32's operands and rows; resolve_plan chooses their towers
     // the tuned towers' layout: whole workgroups of boards, filters in whole 64-channel groups (zero channels), the planes in whole
     // 128-byte rows; the other towers pad nothing
     e->slots = tower_slots(d.board);

@@ -13,6 +13,7 @@
 #include "f16r_rule.h"    // dtype f16r: the epilogue with an f32 residual stream, the lane buffers' roles, the tap layout per point
 #include "head_chain_rule.h"  // the short-chain form of the f32 FC pair: grid map, operand offsets, walk order, epilogues
 #include "t64r_rule.h"    // dtype f16r_resident: that tower in one LDS-resident launch -- who owns an element, the LDS buffers, the layer table
+#include "t64f_rule.h"    // dtype f32_resident: the exact f32 tower in one LDS-resident launch -- LDS plan, step table, ownership map, layer table
 
 namespace cattus {
 
@@ -256,6 +257,20 @@ void launch_tower64(Act act, const Tower64Args& args, uint32_t rows, int ch, boo
 // the per-layer f16r tower (launch_conv3x3_f16r and dtype f16's conv1).  args.sat and args.out required, no fused heads; anything else aborts.
 void launch_tower64_stream(const Tower64Args& args, uint32_t rows, int ch, bool layer_steps, hipStream_t st, hipEvent_t ev_start = nullptr,
                            hipEvent_t ev_stop = nullptr);
+
+// ---- K1rf resident, exact f32 (dtype f32_resident; tower64_f32_kernel in kernels_t64f.hip; t64f_rule.h has the LDS plan, the step table, the
+// ownership map and the layer table): the per-layer f32 tower of a <= 64-filter network in one launch, its bits ----
+struct Tower64F32Args {
+    const uint64_t* planes;      // [n][C][w64] bitboards, C <= 32
+    const Tower64Layer* layers;  // device array [nlayers]: stem ([9][64][32] f32), then (conv1, conv2) per block ([9][64][64] f32); bias [64]; res as t64f_layer().skip
+    float* out;                  // required: [rows][64] f32, the tower output, rows = boards * tower_slots(S)
+    uint32_t n, C, w64, S, nlayers;
+    uint32_t nch;                // 32-channel chunks a hidden layer walks: t64f_hidden_chunks (1 only where channels 32..63 are all zero)
+};
+// rows % 256 == 0; ch = 4: one 64-slot board per workgroup, ch = 2: 128 rows (128-slot boards always); t64f_ch has the rule.  Anything the
+// arguments' comments exclude aborts.
+void launch_tower64_f32(const Tower64F32Args& args, uint32_t rows, int ch, hipStream_t st, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+hipError_t prepare_tower64_f32();  // its dynamic-LDS opt-in; called by prepare_device()
 
 // ---- K1rs resident, split precision: the whole tower of a <= 64-filter f16x2 network in one launch (see kernels.hip) ----
 struct Tower64SplitLayer {

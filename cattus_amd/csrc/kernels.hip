@@ -2080,7 +2080,7 @@ hipError_t prepare_device() {
     for_each_tower64<__bf16>([&](auto kernel, int lds, auto...) { lds_opt_in(err, kernel, lds); });
     for_each_tower64<_Float16>([&](auto kernel, int lds, auto...) { lds_opt_in(err, kernel, lds); });
     for_each_tower64<Tower64Stream>([&](auto kernel, int lds, auto...) { lds_opt_in(err, kernel, lds); });
-    for (hipError_t e : {prepare_tower64_split(), prepare_wino(), prepare_wino4(), prepare_winof4(), prepare_wino4s(), prepare_wino_f16(), prepare_wino_f32(), prepare_splitk()})
+    for (hipError_t e : {prepare_tower64_split(), prepare_tower64_f32(), prepare_wino(), prepare_wino4(), prepare_winof4(), prepare_wino4s(), prepare_wino_f16(), prepare_wino_f32(), prepare_splitk()})
         if (err == hipSuccess) err = e;
     return err;
 }

@@ -38,6 +38,10 @@ _DTYPES_F16R = {"f16r": DTYPE_F16R}
 # 64 filters, where dtype "f16" accepts tower_form "resident").  A table of its own again: the three above stay what they were.
 DTYPE_F16R_RESIDENT = 7
 _DTYPES_F16R_RESIDENT = {"f16r_resident": DTYPE_F16R_RESIDENT}
+# "f32_resident": dtype "f32"'s arithmetic, bit for bit, as a demand for the one-launch LDS-resident form (CATTUS_DTYPE_F32_RESIDENT: at most 64
+# filters and 32 planes).  9, not 8: 8 stays unassigned and invalid.  A table of its own again: the four above stay what they were.
+DTYPE_F32_RESIDENT = 9
+_DTYPES_F32_RESIDENT = {"f32_resident": DTYPE_F32_RESIDENT}
 
 # every symbol include/cattus_hip.h declares
 ABI_SYMBOLS = [
@@ -120,7 +124,7 @@ TOWER_FORMS_RESIDENT = {"resident": 5}
 # `CATTUS_TOWER64=0 python scripts/...` and monkeypatch.setenv keep working.  CATTUS_WINOGRAD=0/1 (rounds 3-4) maps to tower_form.
 DIAG_SWITCHES = ("CATTUS_CONV_CB", "CATTUS_CONV_PBW", "CATTUS_FUSED_STEM", "CATTUS_T64_CH", "CATTUS_T64_LS", "CATTUS_SPLIT_W", "CATTUS_T64S_HEADS",
                  "CATTUS_T64S_SHAPE", "CATTUS_TOWER64", "CATTUS_FORCE_GENERIC", "CATTUS_WINO_INPLACE", "CATTUS_ARENA", "CATTUS_WINO_KERNEL",
-                 "CATTUS_WINO_PERSIST", "CATTUS_WINO_SPIN", "CATTUS_STREAM_SHIFT", "CATTUS_SPLITK_WAYS")
+                 "CATTUS_WINO_PERSIST", "CATTUS_WINO_SPIN", "CATTUS_STREAM_SHIFT", "CATTUS_SPLITK_WAYS", "CATTUS_T64F_NARROW")
 
 
 class Stats(C.Structure):
@@ -359,6 +363,9 @@ class HipEvaluator:
         the BatchNorm estimate's shifts and takes only the headroom guard from the sample, as "f16w" does.
         "f16r_resident" (_DTYPES_F16R_RESIDENT) is "f16r" in ONE LDS-resident launch (tower64_stream_kernel), the same bits: networks of at most 64 filters, where dtype "f16"
         accepts tower_form "resident"; tower_form "auto" and "resident" both mean it, the forms of the "f16x2" tower are ignored, anything it does not cover is refused.
+        "f32_resident" (_DTYPES_F32_RESIDENT) is "f32" in ONE LDS-resident launch (tower64_f32_kernel), the same bits and so the CPU oracle's: networks of at most 64
+        filters and 32 planes with value + policy head channels <= 32; tower_form "auto" and "resident" both mean it, anything it does not cover is refused; like "f32" it has no shadow
+        (``verify`` / ``trace`` are refused) and nothing to calibrate.
         tower_form: "auto" | "direct" | "winograd" | "winograd_f4" | "direct_splitk" (cattus_tower_form; None = "auto", or what CATTUS_WINOGRAD=0/1 in the
         environment says; "winograd_f4", the F(4x4,3x3) form, and "direct_splitk", the direct form with the K walk divided over a workgroup's waves
         for batches of a few leaves, are opt-in only: never what "auto" picks, and each has bits of its own; "resident" (TOWER_FORMS_RESIDENT)
@@ -390,7 +397,8 @@ class HipEvaluator:
         if switches is None:
             switches = {k: os.environ[k] for k in DIAG_SWITCHES if k in os.environ}
         self.tower_form = tower_form
-        cfg = EvalConfig(C.sizeof(EvalConfig), device, self.batch_size, self.plane_words, {**_DTYPES_F16R_RESIDENT, **_DTYPES, **_DTYPES_WINO_F32, **_DTYPES_F16R}[dtype], flush_us, {**TOWER_FORMS, **TOWER_FORMS_RESIDENT}[tower_form], int(tail_leaves))
+        dtype_value = _DTYPES_F32_RESIDENT[dtype] if dtype in _DTYPES_F32_RESIDENT else {**_DTYPES_F16R_RESIDENT, **_DTYPES, **_DTYPES_WINO_F32, **_DTYPES_F16R}[dtype]
+        cfg = EvalConfig(C.sizeof(EvalConfig), device, self.batch_size, self.plane_words, dtype_value, flush_us, {**TOWER_FORMS, **TOWER_FORMS_RESIDENT}[tower_form], int(tail_leaves))
         h = C.c_void_p()
         buf = C.create_string_buffer(blob, len(blob))
         text = ";".join(f"{k}={v}" for k, v in switches.items()).encode() if switches else None

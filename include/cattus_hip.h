@@ -159,6 +159,45 @@ typedef enum cattus_dtype {
      * margin (+3.7 % there, +2 - 4 % over the five shapes).  Not measured: in-kernel stamps or counters of tower64_stream_kernel, filter
      * counts other than 64 and 16 (padded to 64), two evaluators sharing a device, self-play. */
     CATTUS_DTYPE_F16R_RESIDENT = 7,
+    /* (8 is unassigned and stays CATTUS_E_INVALID.) */
+    /* CATTUS_DTYPE_F32's arithmetic, BIT FOR BIT -- and so the CPU oracle's -- as a demand for the ONE-LAUNCH LDS-RESIDENT form (K1rf,
+     * tower64_f32_kernel): every logit and every value equal what the same blob returns from CATTUS_DTYPE_F32, for every n, through every
+     * entry point (tests/test_f32_resident_gpu.py); cattus_stats.saturated stays 0.  Behaviour of CATTUS_DTYPE_F32, of every other dtype
+     * and of every tower_form is unchanged, and AUTO never picks this plan; it is a dtype value because CATTUS_DTYPE_F32 with RESIDENT
+     * stays refused and this struct stays 32 bytes.  One launch runs plane expansion, stem and every residual block: 512 threads, four
+     * MFMA consumer waves and four LDS-DMA loader waves, 64 rows per workgroup (one 64-slot board, while the batch has at most 256 padded
+     * boards) or 128 (two 64-slot boards, or one 128-slot board); the per-layer kernel's 3-slab weight ring in front of two f32
+     * activation buffers of two 32-channel chunks each (107,008 / 139,776 B of LDS).  Per output element the operations are
+     * conv3x3_mfma_v2_kernel<float>'s in its order: one v_mfma_f32_32x32x2_f32 chain over (chunk) x (kernel row) x (3 taps x 4 k-slices), +
+     * bias, + skip, ReLU; no rounding, no clamp, no stream shift.  A network of at most 32 filters walks chunk 0 of its hidden layers only
+     * (half the MFMAs, the same bits: the dropped terms are fmaf(0, 0, acc); diagnostic switch CATTUS_T64F_NARROW=0 walks both).  The last
+     * layer leaves as the f32 rows the per-layer tower writes and the two f32 head launches follow unchanged.  Weights, biases and head
+     * matrices are CATTUS_DTYPE_F32's uploads.
+     * Coverage: at most 64 (padded) filters, vhc + phc <= 32, at most 32 planes, no CATTUS_TOWER64=0; any board up to 11x11, any block
+     * count including 0 -- anything else is CATTUS_E_UNSUPPORTED (never other bits under this name; CATTUS_DTYPE_F32 runs every shape per
+     * layer).  A SimpleTwoHeadedModel blob runs in f32, as under every dtype.  tower_form: AUTO and RESIDENT both mean this form; DIRECT,
+     * WINOGRAD, WINOGRAD_F4 and DIRECT_SPLITK are ignored as under CATTUS_DTYPE_F32.  tail_leaves is ignored.  cattus_hip_time_tower reports
+     * 1 launch, cattus_hip_tower_kernel "tower64_f32_kernel".  Observation (cattus_hip_tap) runs the per-layer CATTUS_DTYPE_F32 pass on the
+     * same buffers: the same bits.  cattus_hip_verify / cattus_hip_trace are CATTUS_E_UNSUPPORTED as for CATTUS_DTYPE_F32 (the shadow would
+     * be itself; the shadow and the calibration evaluator of other dtypes keep the per-layer f32 tower), cattus_hip_stream_range stays
+     * CATTUS_E_UNSUPPORTED (it measures on the per-layer tower), cattus_hip_create_calibrated has nothing to calibrate and is
+     * cattus_hip_create, cattus_hip_head_chain applies as under CATTUS_DTYPE_F32.
+     * MEASURED on one MI355X (scripts/f32_resident_time.py -> profiles/f32_resident.txt: one process, max_batch = n, the evaluators
+     * alternating over three rounds, 300 steps through cattus_hip_eval_device, min; F32_RESIDENT | F32 | F16X2 | F16R_RESIDENT, ms per step):
+     *   hex7 6x64:  32 leaves 0.142 | 0.168 | 0.053 | 0.041,  128: 0.143 | 0.171 | 0.053 | 0.042,  512: 0.250 | 0.309 | 0.089 | 0.059
+     *     (the tower: one launch of 125.6 / 126.7 / 233.8 us against 13 of 11.3 / 11.5 / 22.0 us);
+     *   chess 7x16 (the narrow walk): 64 leaves 0.100 | 0.195 | 0.060 | 0.050,  256: 0.102 | 0.206 | 0.062 | 0.053  (one launch of 81.5 /
+     *     82.6 us against 15 of 11.4 / 12.1; with CATTUS_T64F_NARROW=0 146.1 / 147.2 us and 0.164 / 0.166 ms per step: the narrow walk
+     *     takes 0.61x that step, the same bits).
+     * The yardstick is CATTUS_DTYPE_F32 in the same process on the same binary; against the 12 % by which two boxes differ on one binary:
+     * RECOMMENDED OVER CATTUS_DTYPE_F32 ON ALL FIVE SHAPES, narrowly on hex7 6x64 (16 / 17 / 19 % less time per step, the same bits) and
+     * clearly on chess 7x16 (49 / 51 %); no shape was measured on which it is not.  It stays 1.6-2.8x F16X2's step and 1.9-4.3x
+     * F16R_RESIDENT's: the exact tower for checks, not a throughput mode.  The estimate it was built on (hex7
+     * 6x64 at 128 leaves 0.18 -> 0.115-0.125 ms, 30-35 % less; chess 7x16 0.07-0.08) WAS MISSED: 0.143 and 0.100.  A step of 48 MFMAs
+     * costs 1.54 us in the launch (from the two walks of chess 7x16), 64 cycles per MFMA at about 2.0 GHz where the estimate took 2.4.
+     * Not measured: in-kernel stamps or counters of tower64_f32_kernel, the clock under this load, filter counts other than 64 and 16
+     * (padded to 64), two evaluators sharing a device, self-play. */
+    CATTUS_DTYPE_F32_RESIDENT = 9,
 } cattus_dtype;
 /* Every dtype takes any network the blob format and the plane pack allow: up to 128 plane words per leaf (planes x plane_words),
  * e.g. AlphaZero's 119 chess planes. */

@@ -28,6 +28,11 @@ pub enum HipDtype {
     /// the bits of dtype f16r (`CATTUS_DTYPE_F16R_RESIDENT`), about half `F16`'s per-leaf error; refused where the form does not cover the network
     #[serde(rename = "f16r_resident")]
     F16rResident = 7,
+    /// (8 is unassigned)
+    /// exact f32 with the whole tower in one LDS-resident launch: networks of at most 64 filters and 32 planes; the bits of `F32`
+    /// (`CATTUS_DTYPE_F32_RESIDENT`); refused where the form does not cover the network
+    #[serde(rename = "f32_resident")]
+    F32Resident = 9,
 }
 
 #[repr(C)]
