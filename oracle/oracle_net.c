@@ -100,9 +100,12 @@ ORACLE_API float oracle_tanhf(float x) {
     float t;
     if (!(ax == ax)) return x; /* NaN */
     if (ax < 0.5f) {
-        /* odd Taylor series to x^13; |err| < 3e-8 relative on [0,0.5) */
+        /* odd Taylor series to x^15; within 0.8 ulp on [0,0.5) (every f32 there checked against float64) and non-decreasing
+         * from one f32 to the next.  The series to x^13 was 1.9 ulp high at the top of the range (the x^15 term is 4.4e-8 at 0.5):
+         * the value an ulp below 0.5 lay an ulp above the exp branch's at 0.5. */
         float s = ax * ax;
-        float p = 21844.0f / 6081075.0f;
+        float p = -929569.0f / 638512875.0f;
+        p = fmaf(p, s, 21844.0f / 6081075.0f);
         p = fmaf(p, s, -1382.0f / 155925.0f);
         p = fmaf(p, s, 62.0f / 2835.0f);
         p = fmaf(p, s, -17.0f / 315.0f);

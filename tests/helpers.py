@@ -7,7 +7,7 @@ from pathlib import Path
 
 import numpy as np
 
-from cattus_amd.weights import BN_EPS, NetDesc, seeded_blob
+from cattus_amd.weights import BN_EPS, NetDesc, seeded_blob, seeded_tensors
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
 
@@ -50,24 +50,47 @@ def planes_to_f64(planes: np.ndarray, board: int) -> np.ndarray:
     return bits.astype(np.float64).reshape(len(planes), planes.shape[1], board, board)
 
 
-def forward_f64(desc: NetDesc, tensors: dict, planes: np.ndarray):
-    """The network in float64 on the CPU, built from the raw tensors (the seeded_tensors / pack_tensors input) and not from a
-    blob, so that a packing or BatchNorm-folding error of the blob path cannot cancel out.  Returns (policy, value) as float64."""
+def _net_f64(desc: NetDesc, tensors: dict):
     import torch
 
-    from cattus_amd.torch_model import PolicyValueNet
+    from cattus_amd.torch_model import PolicyValueNet, SimpleTwoHeaded
 
-    net = PolicyValueNet(desc).to(torch.float64)
+    net = (SimpleTwoHeaded(desc) if desc.simple else PolicyValueNet(desc)).to(torch.float64)
     sd = net.state_dict()
     for k in sd:
         if k.endswith("num_batches_tracked"):
             continue
         sd[k] = torch.from_numpy(np.asarray(tensors[k], dtype=np.float64).reshape(tuple(sd[k].shape)))
     net.load_state_dict(sd, strict=True)
-    net.eval()
+    return net.eval()
+
+
+def forward_f64(desc: NetDesc, tensors: dict, planes: np.ndarray):
+    """The network in float64 on the CPU, built from the raw tensors (the seeded_tensors / pack_tensors input) and not from a
+    blob, so that a packing or BatchNorm-folding error of the blob path cannot cancel out.  Returns (policy, value) as float64."""
+    import torch
+
     with torch.no_grad():
-        p, v = net(torch.from_numpy(planes_to_f64(planes, desc.board)))
+        p, v = _net_f64(desc, tensors)(torch.from_numpy(planes_to_f64(planes, desc.board)))
     return p.numpy(), v.numpy().reshape(-1)
+
+
+def value_preactivation_f64(desc: NetDesc, tensors: dict, planes: np.ndarray) -> np.ndarray:
+    """What forward_f64's value is the tanh of: the value head's last linear layer in float64, ``[n]``."""
+    import torch
+
+    net = _net_f64(desc, tensors)
+    with torch.no_grad():
+        x = torch.from_numpy(planes_to_f64(planes, desc.board))
+        if desc.simple:
+            pre = net._value_head(torch.relu(net._dense2(torch.relu(net._dense1(x.flatten(1))))))
+        else:
+            x = net._cbr(net._conv1, x)
+            for b in net._residual_blocks:
+                x = torch.relu(x + b._bn2(b._conv2(torch.relu(b._bn1(b._conv1(x))))))
+            v = net._cbr(net._value_head["0"], x).flatten(1)
+            pre = net._value_head["4"](torch.relu(net._value_head["2"](v)))
+    return pre.numpy().reshape(-1)
 
 
 # the single-term f16 tower (11 significant bits) against the bf16 one (8): its error on the same leaves is at most a quarter
@@ -176,3 +199,112 @@ CHANNEL_PATTERNS = {
     "M8": lambda F: np.where(np.arange(F) % 4 == 1, 0, -8),  # a small median, every fourth channel 2^8 above it
     "S8": lambda F: (7 * np.arange(F)) % 17 - 8,  # an even spread over 2^-8 .. 2^8
 }
+
+
+# ---- the dial network: a network whose outputs the caller sets through the input planes ----
+DIAL_LADDER_TOP, DIAL_LADDER_BITS = 5, 32  # value FC2's weights: 2^5 down to 2^-26, then the same negated
+DIAL_SHIFT = -128.0  # what bit 0 of plane 1 adds to the logits of the band
+
+
+def _dial_var() -> np.float32:
+    """The f32 running_var v with f32(v + f32(1e-5)) == 1: sqrtf of it is 1, and the folded scale gamma / sqrtf(var + eps) is gamma."""
+    eps = np.float32(BN_EPS)
+    v = np.float32(1.0) - eps
+    for _ in range(8):
+        s = np.float32(v + eps)
+        if s == np.float32(1.0):
+            return v
+        v = np.nextafter(v, np.float32(0.0 if s > 1 else 2.0), dtype=np.float32)
+    raise AssertionError("no f32 variance folds to a unit scale")
+
+
+DIAL_VAR = _dial_var()
+
+
+def dial_bits(target: float) -> int:
+    """Plane 0 of the leaf whose pre-tanh value is ``target``: pixel j < 32 carries 2^(5 - j), pixel 32 + j carries -2^(5 - j).  Raises
+    ValueError where the ladder cannot represent the target exactly (|target| >= 64, a bit below 2^-26, not finite); a target that
+    the ladder holds has at most 24 significant bits only if it is an f32 number, which is checked too."""
+    t = float(target)
+    if not math.isfinite(t) or float(np.float32(t)) != t:
+        raise ValueError(f"dial: target {target!r} is not an f32 number")
+    low = DIAL_LADDER_TOP - DIAL_LADDER_BITS + 1  # -26
+    scaled = abs(t) * 2.0**-low
+    m = int(scaled)
+    if m != scaled or m >= 1 << DIAL_LADDER_BITS:
+        raise ValueError(f"dial: target {target!r} is not a sum of 2^{DIAL_LADDER_TOP} .. 2^{low}")
+    word = 0
+    for j in range(DIAL_LADDER_BITS):
+        if (m >> (DIAL_LADDER_BITS - 1 - j)) & 1:
+            word |= 1 << (j + (DIAL_LADDER_BITS if t < 0 else 0))
+    return word
+
+
+def dial_tensors(desc: NetDesc, value_targets=None, logit_table=None, band=None, block_seed: int = 11):
+    """Raw tensors (the seeded_tensors / pack_tensors format) of a network of shape ``desc`` whose outputs the caller chooses
+    through the input planes, and the dict dial_planes needs to encode them.
+
+      stem         filter 0 copies plane 0, filter 1 copies plane 1 (centre tap 1, every other weight 0; gamma 1, beta 0, mean 0,
+                   running_var DIAL_VAR: the folded scale is exactly 1 in f32); every other filter is dead (gamma = beta = 0)
+      blocks       seeded convs and statistics under _bn2 gamma = beta = 0: the identity on the stream
+      value head   conv channel 0 reads filter 0 (weight 1, mean 0, DIAL_VAR), the others are zero; FC1 row k < 64 has a single 1 at
+                   (channel 0, pixel k), bias 0: h1[k] = bit k of plane 0; FC2 = 2^5 .. 2^-26, then -2^5 .. -2^-26, then zeros, b2 = 0
+      policy head  conv channel 0 reads filter 1; the FC is zero except DIAL_SHIFT at (move in ``band``, channel 0, pixel 0), its bias is
+                   ``logit_table`` (f32 [moves]; default zeros; inf and NaN entries come back scrubbed): logit m = table[m], and
+                   table[m] - 128 for m in the band of a leaf with bit 0 of plane 1 set
+
+    Every weight and every activation is 0, 1 or a power of two, exact in f32, f16 and bf16, and a target with at most 24
+    significant bits is an exact sum of its ladder terms in any order.  ``value_targets``: checked here against the ladder
+    (ValueError), so a test's table of targets fails where it is built.  Needs at least two planes, two filters and 64 pixels."""
+    if desc.simple or desc.planes < 2 or desc.filters < 2 or desc.hw < 2 * DIAL_LADDER_BITS or desc.vhc < 1 or desc.phc < 1:
+        raise ValueError(f"dial_tensors: {desc} has no room for the dial")
+    for t in () if value_targets is None else value_targets:
+        dial_bits(t)
+    table = np.zeros(desc.moves, dtype=np.float32) if logit_table is None else np.asarray(logit_table, dtype=np.float32)
+    if table.shape != (desc.moves,):
+        raise ValueError(f"dial_tensors: logit_table has shape {table.shape}, want ({desc.moves},)")
+    band = np.zeros(0, dtype=np.int64) if band is None else np.asarray(band, dtype=np.int64)
+    if band.size and not (0 <= band.min() and band.max() < desc.moves):
+        raise ValueError("dial_tensors: band outside the moves")
+    f, hw = desc.filters, desc.hw
+    seeded = seeded_tensors(desc, block_seed)
+    out = {k: np.zeros_like(v) for k, v in seeded.items()}
+    for k in out:
+        if k.endswith("running_var"):
+            out[k][...] = DIAL_VAR
+    out["_conv1._conv.weight"][0, 0, 1, 1] = 1.0
+    out["_conv1._conv.weight"][1, 1, 1, 1] = 1.0
+    out["_conv1._bn.weight"][:2] = 1.0
+    for i in range(desc.blocks):
+        p = f"_residual_blocks.{i}."
+        for k in ("_conv1.weight", "_bn1.running_mean", "_bn1.running_var", "_conv2.weight", "_bn2.running_mean", "_bn2.running_var"):
+            out[p + k] = seeded[p + k].copy()
+    out["_value_head.0._conv.weight"][0, 0, 0, 0] = 1.0
+    k = np.arange(2 * DIAL_LADDER_BITS)
+    out["_value_head.2.weight"][k, k] = 1.0  # input index = channel 0 * hw + pixel k
+    ladder = np.ldexp(1.0, DIAL_LADDER_TOP - np.arange(DIAL_LADDER_BITS)).astype(np.float32)
+    out["_value_head.4.weight"][0, : 2 * DIAL_LADDER_BITS] = np.concatenate([ladder, -ladder])
+    out["_policy_head.0._conv.weight"][0, 1, 0, 0] = 1.0
+    out["_policy_head.2.weight"][band, 0] = DIAL_SHIFT
+    out["_policy_head.2.bias"] = table.copy()
+    assert f >= 2 and out["_value_head.2.weight"].shape[1] == desc.vhc * hw
+    return out, {"band": band, "table": table, "shift": np.float32(DIAL_SHIFT)}
+
+
+def dial_planes(desc: NetDesc, targets, shift_bits=None, seed: int = 0) -> np.ndarray:
+    """uint64 ``[n, planes, words]`` leaves of a dial network: leaf i's value is tanh(targets[i]) and, where shift_bits[i], the logits
+    of its band are lowered by 128.  The planes from the third on feed nothing and carry seeded noise.  Raises ValueError on a target
+    that the ladder cannot represent exactly."""
+    n = len(targets)
+    shift_bits = np.zeros(n, dtype=bool) if shift_bits is None else np.asarray(shift_bits, dtype=bool)
+    if shift_bits.shape != (n,):
+        raise ValueError("dial_planes: one shift bit per target")
+    words = (desc.hw + 63) // 64
+    rng = np.random.default_rng(seed)
+    planes = rng.integers(0, 2**63, size=(n, desc.planes, words), dtype=np.uint64)
+    for w in range(words):
+        planes[:, :, w] &= np.uint64((1 << min(64, desc.hw - 64 * w)) - 1)
+    planes[:, :2] = 0
+    planes[:, 0, 0] = np.array([dial_bits(t) for t in targets], dtype=np.uint64)
+    planes[:, 1, 0] = shift_bits.astype(np.uint64)
+    return planes

@@ -97,6 +97,68 @@ def test_hip_simple_model_bit_exact_vs_oracle(name, dtype):
     assert outputs_equal_ref_tol(got_p, got_v, z["policy"], z["value"])
 
 
+def _saturating_simple_model():
+    """A seeded TTT SimpleTwoHeadedModel with its value head (weight and bias) times 2^6 -- exact, and the 1024 leaves' pre-tanh values
+    then spread from 0.016 to 24, across both branch points of the evaluator's tanh (0.5 and 10), where a seeded one stays below 0.4.
+    Returns (desc, blob, planes, float64 values, bound): the bound is test_output_range's tanh bar plus the f32 rounding of the
+    pre-activation through tanh' = 1 - v^2.  That rounding, a priori: a dot product of K terms taken as one fmaf chain plus the bias
+    errs by at most (K + 1) u (|w| . |x| + |b|), u = 2^-24, and an error e of the inputs adds |w| . e (ReLU does not enlarge it);
+    carried through the two dense layers and the value head in float64."""
+    from cattus_amd.weights import pack_tensors, seeded_tensors
+    from helpers import forward_f64, planes_to_f64
+    from test_output_range import TANH_ATOL, TANH_RTOL
+
+    d = simple_desc(**TTT)
+    t = seeded_tensors(d, 7)
+    t["_value_head.weight"] = t["_value_head.weight"] * np.float32(64.0)
+    t["_value_head.bias"] = t["_value_head.bias"] * np.float32(64.0)
+    planes = synth.random_ttt_planes(1024, 9)
+    _, v64 = forward_f64(d, t, planes)
+    x = planes_to_f64(planes, d.board).reshape(len(planes), -1)
+    e, u = np.zeros_like(x), 2.0**-24
+    for name, relu in (("_dense1", True), ("_dense2", True), ("_value_head", False)):
+        w, b = t[name + ".weight"].astype(np.float64), t[name + ".bias"].astype(np.float64)
+        e = (w.shape[1] + 1) * u * (np.abs(x) @ np.abs(w).T + np.abs(b)) + e @ np.abs(w).T
+        x = x @ w.T + b
+        pre = x
+        if relu:
+            x = np.maximum(x, 0.0)
+    pre, e = pre.reshape(-1), e.reshape(-1)
+    assert (np.abs(pre) < 0.5).sum() >= 3 and ((np.abs(pre) >= 0.5) & (np.abs(pre) < 10)).sum() >= 50 and (np.abs(pre) >= 10.5).sum() >= 50
+    assert np.abs(np.tanh(pre) - v64).max() < 1e-14
+    bound = TANH_RTOL * np.abs(v64) + TANH_ATOL + e * (1.0 - v64 * v64 + 2 * e)
+    return d, pack_tensors(d, t), planes, v64, bound
+
+
+def test_oracle_simple_model_tanh_over_its_whole_range():
+    """The oracle's tanh behind dense layers, in all three of its branches, against float64 (measured: max |dv| 3.2e-6 -- the pre-activation's
+    own f32 rounding, times 64 -- at 0.0017 of the a-priori bound; the sharp check is the GPU test's, bit for bit against this oracle)."""
+    d, blob, planes, v64, bound = _saturating_simple_model()
+    _, v = oracle.OracleNet(blob).forward(planes)
+    err = np.abs(v.astype(np.float64) - v64)
+    print("simple model, value head x 64: oracle vs f64 max |dv| %.3g, max err / bound %.3g" % (err.max(), (err / bound).max()))
+    assert (err <= bound).all() and (np.abs(v) <= 1).all() and (np.abs(v) == 1).sum() >= 50
+
+
+@pytest.mark.gpu
+def test_hip_simple_model_tanh_over_its_whole_range():
+    """policy_fc_kernel<DENSE_TANH> (launch_dense) in all three branches of tanh_exact: the oracle's bits, and within the same bound of
+    float64."""
+    from cattus_amd.evaluator import HipEvaluator
+
+    d, blob, planes, v64, bound = _saturating_simple_model()
+    want_p, want_v = oracle.OracleNet(blob).forward(planes)
+    with HipEvaluator(blob, batch_size=1024, plane_words=1, dtype="f32", switches={}) as ev:
+        p, v = ev.eval(planes)
+        one_p, one_v = ev.eval(planes[100:101])
+        assert ev.tower_kernel() == "policy_fc_kernel"
+    err = np.abs(v.astype(np.float64) - v64)
+    print("simple model, value head x 64: HIP vs f64 max |dv| %.3g, max err / bound %.3g" % (err.max(), (err / bound).max()))
+    assert v.tobytes() == want_v.tobytes() and p.tobytes() == want_p.tobytes()
+    assert one_v.tobytes() == want_v[100:101].tobytes() and one_p.tobytes() == want_p[100:101].tobytes()
+    assert (err <= bound).all() and (np.abs(v) <= 1).all() and (np.abs(v) == 1).sum() >= 50
+
+
 @pytest.mark.gpu
 def test_hip_simple_model_full_batches_and_threads():
     """Ragged and full batches (batch rows are independent), and the blocking per-leaf entry point from many threads."""
