@@ -13,7 +13,7 @@ ROOT = PKG.parent
 
 HIP_LIB = PKG / "libcattus_hip.so"
 HIP_SOURCES = [CSRC / "kernels.hip", CSRC / "kernels_t64s.hip", CSRC / "kernels_t64f.hip", CSRC / "kernels_wino.hip", CSRC / "kernels_wino4.hip", CSRC / "kernels_winof4.hip", CSRC / "kernels_wino4s.hip", CSRC / "kernels_wino_f16.hip", CSRC / "kernels_wino_f32.hip", CSRC / "kernels_splitk.hip", CSRC / "kernels_head_chain.hip", CSRC / "evaluator.hip"]
-HIP_DEPS = HIP_SOURCES + [CSRC / "kernels.h", CSRC / "frag_index.h", CSRC / "winof4_rule.h", CSRC / "wino4s_rule.h", CSRC / "wino_f16_rule.h", CSRC / "wino_f32_rule.h", CSRC / "splitk_rule.h", CSRC / "f16r_rule.h", CSRC / "t64r_rule.h", CSRC / "t64f_rule.h", CSRC / "head_chain_rule.h", CSRC / "weight_layout.h", CSRC / "verify_rule.h", CSRC / "prior_rule.h", CSRC / "legal_span.h", CSRC / "tap_layout.h", CSRC / "device_common.h", ROOT / "include" / "cattus_hip.h"]
+HIP_DEPS = HIP_SOURCES + [CSRC / "kernels.h", CSRC / "frag_index.h", CSRC / "winof4_rule.h", CSRC / "wino4s_rule.h", CSRC / "wino_f16_rule.h", CSRC / "wino_f32_rule.h", CSRC / "splitk_rule.h", CSRC / "f16r_rule.h", CSRC / "t64r_rule.h", CSRC / "t64f_rule.h", CSRC / "head_chain_rule.h", CSRC / "head_fuse_rule.h", CSRC / "weight_layout.h", CSRC / "verify_rule.h", CSRC / "prior_rule.h", CSRC / "legal_span.h", CSRC / "tap_layout.h", CSRC / "device_common.h", ROOT / "include" / "cattus_hip.h"]
 
 # -ffp-contract=off: the f32 path promises a fixed fmaf-chain order, so the compiler
 # must not fuse or split any multiply-add on its own, on the device or in the host-side BN folding.

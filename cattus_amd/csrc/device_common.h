@@ -270,6 +270,67 @@ __device__ __forceinline__ float tanh_exact(float x) {
     return x < 0.0f ? -t : t;
 }
 
+// ---- the f32 head convs in a resident tower's tail (cattus_hip_fused_heads; head_fuse_rule.h has the LDS plan, the ownership map, the
+// chain's order and the hv index) ----
+// The operands' way into LDS: the four loader waves, once they have issued and awaited their last weight slab, copy the [32][64] f32 head
+// weights to the pitched image at lds_w and the 32 biases to lds_b -- under the consumers' last step, into bytes that are dead behind that
+// step's barrier -- and then meet the consumers at the barrier that orders these stores (and the consumers' staged rows) against the chain's
+// fragment reads.  t: 0 .. HF_STAGE_THREADS - 1.
+__device__ __forceinline__ void hf_stage_operands(const float* head_w, const float* head_b, char* lds_w, char* lds_b, int t) {
+    typedef const __attribute__((address_space(1))) f32x4* gf32x4p;
+    typedef const __attribute__((address_space(1))) float* gf32p;
+    const gf32x4p w = (gf32x4p)head_w;
+    const f32x4 v0 = w[t], v1 = w[t + HF_STAGE_THREADS];
+    const float bv = ((gf32p)head_b)[t & 31];
+    *reinterpret_cast<f32x4*>(lds_w + hf_piece_dst(t)) = v0;
+    *reinterpret_cast<f32x4*>(lds_w + hf_piece_dst(t + HF_STAGE_THREADS)) = v1;
+    if (t < HF_CHANNELS) *reinterpret_cast<float*>(lds_b + t * 4) = bv;
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+// The chain and its epilogue, behind that barrier: the consumer wave that owns a 32-row tile (hf_tile_of_wave) runs head_conv_tile<float>'s
+// eight stages -- all sixteen fragment reads issued ahead of the first MFMA, as there -- and writes acc + bias, ReLU to hv for the rows of
+// the pass's n leaves that are pixels of a board and the channels the heads have.  row_frag(row, u, h): LDS byte address of tower row
+// `row`'s fragment of stage u for lane half h.  A: the tower's arguments (Tower64Args: n, S, hv, hv_pol, kvp, kpp, vhc, ocn).
+template <int CH, class Args, class RowFrag>
+__device__ __forceinline__ void hf_head_convs(const char* smem, const HfLds& lds, RowFrag row_frag, int wave, int lane, int row0, uint32_t slots, const Args& A) {
+    if (hf_tile_of_wave(CH, wave) < 0) return;
+    const int r = lane & 31, h = lane >> 5;
+    const int row = hf_own(CH, wave, lane, 0).row;
+    f32x4 hb[4];
+#pragma unroll
+    for (int g = 0; g < 4; g++) hb[g] = *reinterpret_cast<const f32x4*>(smem + lds.b + (8 * g + 4 * h) * 4);
+    f32x4 fa[8], fb[8];
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+        fa[u] = *reinterpret_cast<const f32x4*>(smem + lds.w + hf_w_frag(r, u, h));
+        fb[u] = *reinterpret_cast<const f32x4*>(smem + row_frag(row, u, h));
+    }
+    f32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; e++) acc[e] = 0.0f;
+#pragma unroll
+    for (int u = 0; u < 8; u++) Mfma<float>::mac(fa[u], fb[u], acc);
+    const HfHead H{A.S * A.S, A.vhc, A.ocn, A.kvp, A.kpp, A.hv_pol, slots};
+    const uint32_t grow = (uint32_t)(row0 + row);
+    float* const hv = reinterpret_cast<float*>(A.hv);
+#pragma unroll
+    for (int e = 0; e < 16; e++) {
+        const uint32_t i = (uint32_t)hf_own(CH, wave, lane, e).channel;
+        if (!hf_writes(H, A.n, grow, i)) continue;
+        const float y = acc[e] + hb[e >> 2][e & 3];
+        hv[hf_hv_index(H, grow, i)] = y > 0.0f ? y : 0.0f;
+    }
+}
+
+// The HEADS instance of a resident tower is entered through this one kernel: Tower::run is the tower's body with the flag on,
+// Tower::Args its argument struct, Tower::MIN_WAVES its twin's second launch bound.  (A name of its own: the twins' names keep meaning the
+// instances they always meant, in scripts/kernel_regs.py's listing as everywhere.)
+template <class Tower>
+__global__ void __launch_bounds__(512, Tower::MIN_WAVES) tower_heads_kernel(typename Tower::Args A) {
+    Tower::run(A);
+}
+
 // ---- host side: a kernel family's instances, listed once ----
 // Next to its kernels every templated family has one for_each_* visitor.  It calls f(kernel, ..., template arguments as
 // std::integral_constant values) for every instance that exists; an `if constexpr` on the family's rule keeps the other

@@ -406,6 +406,11 @@ struct cattus_eval {
     // head_chain_batches counts those passes.  Written with every lane mutex held, read by a pass under its lane's
     std::atomic<uint32_t> head_chain{0};
     std::atomic<uint64_t> head_chain_batches{0};
+    // cattus_hip_fused_heads as it holds (0 wherever head_fuse_rule.h's hf_takes says the plan has no HEADS instance): an unobserved, untimed pass
+    // launches the resident tower's HEADS instance, which runs the head convs in its tail, and no head conv launch; fused_heads_batches counts
+    // those passes.  Written and read as head_chain is.
+    std::atomic<uint32_t> fused_heads{0};
+    std::atomic<uint64_t> fused_heads_batches{0};
     int splitk_forced = 0;  // CATTUS_SPLITK_WAYS=1|2|4|8: the way count of the split-K direct form (tests and A/B; 0: splitk_rule.h's rule)
     // the f16 towers carry the residual stream at 2^stream_shift times its size, channel k of it at 2^stream_shifts[k] >= that
     // (choose_stream_shift; from cattus_hip_create_calibrated: calibrated_stream_shifts, whose headroom guard can take a channel
@@ -867,7 +872,15 @@ struct Forward {
         ta.hv_pol = hv_leaves(e) * e->kvp, ta.kvp = e->kvp, ta.kpp = e->kpp, ta.vhc = d.vhc, ta.ocn = d.vhc + d.phc;
     }
 
-    // bf16: the head convs fused, nullptr; f16: the tower's output as plain f32 rows in `a` for the f32 head kernels
+    // cattus_hip_fused_heads on this pass (an observed pass never gets here: it runs the per-layer twin): the HEADS instance of the plan's
+    // resident kernel writes hv itself, so the pass fills the head convs' arguments, counts, and hands heads_mfma no tower
+    bool fuse_heads_now() {
+        if (obs || tt || !e->fused_heads.load(std::memory_order_relaxed)) return false;
+        e->fused_heads_batches.fetch_add(1, std::memory_order_relaxed);
+        return true;
+    }
+
+    // bf16: the head convs fused, nullptr; f16: the tower's output as plain f32 rows in `a` for the f32 head kernels (fused_heads: as bf16)
     // 128-row workgroups; for 64-slot boards one board per workgroup while that leaves no CU with two of them
     int resident64_ch(uint32_t rows) const {
         if (e->t64_force_ch) return e->t64_force_ch == 4 && e->slots == 64 ? 4 : 2;  // A/B runs, the row-split test
@@ -876,21 +889,22 @@ struct Forward {
 
     const void* resident64() {
         Tower64Args ta{};
-        const bool f16 = e->act == Act::F16;
-        resident_args(ta, !f16);
-        if (f16) ta.out = a, ta.sat = e->conv_opts.saturated;
+        const bool f16 = e->act == Act::F16, fuse = f16 && fuse_heads_now();
+        resident_args(ta, !f16 || fuse);
+        if (f16) ta.out = fuse ? nullptr : a, ta.sat = e->conv_opts.saturated;
         const uint32_t rows = nb * e->slots;
         hipEvent_t s0 = ev(), s1 = ev();
         launch_tower64(e->act, ta, rows, resident64_ch(rows), e->t64_layer_steps, st, s0, s1);
-        return f16 ? ta.out : nullptr;
+        return ta.out;  // (bf16: none asked for)
     }
 
     // dtype f16r_resident: the tower's output, the f32 stream behind the last layer, as plain f32 rows in the stream's buffer for the f32 head kernels
     const void* resident64_stream() {
         void* const buf[3] = {L.a.p, L.t.p, L.y.p};
         Tower64Args ta{};
-        resident_args(ta, false);
-        ta.out = buf[f16r_head_input()], ta.sat = e->conv_opts.saturated;
+        const bool fuse = fuse_heads_now();
+        resident_args(ta, fuse);
+        ta.out = fuse ? nullptr : buf[f16r_head_input()], ta.sat = e->conv_opts.saturated;
         const uint32_t rows = nb * e->slots;
         hipEvent_t s0 = ev(), s1 = ev();
         launch_tower64_stream(ta, rows, resident64_ch(rows), e->t64_layer_steps, st, s0, s1);
@@ -1457,6 +1471,37 @@ CATTUS_API int cattus_hip_head_chain_leaves(const cattus_eval* e, uint32_t* effe
 CATTUS_API int cattus_hip_head_chain_batches(cattus_eval* e, uint64_t* batches) {
     if (!e || !batches) return fail(CATTUS_E_INVALID, "NULL argument");
     *batches = e->head_chain_batches.load(std::memory_order_relaxed);
+    return CATTUS_OK;
+}
+
+// head_fuse_rule.h's name for this evaluator's tower plan
+static HfPlan fused_heads_plan(const cattus_eval* e) {
+    switch (e->plan.kind) {
+        case TowerKind::Resident64: return e->act == Act::F16 ? HfPlan::Resident64F16 : HfPlan::Resident64Bf16;
+        case TowerKind::Resident64Split: return HfPlan::Resident64Split;
+        case TowerKind::Resident64Stream: return HfPlan::Resident64Stream;
+        case TowerKind::Resident64F32: return HfPlan::Resident64F32;
+        default: return HfPlan::Other;
+    }
+}
+
+CATTUS_API int cattus_hip_fused_heads(cattus_eval* e, uint32_t on) {
+    if (!e) return fail(CATTUS_E_INVALID, "NULL argument");
+    std::unique_lock<std::mutex> held[NLANES];  // every lane, in lane order: batches in flight finish first, none starts meanwhile
+    for (int i = 0; i < NLANES; i++) held[i] = std::unique_lock<std::mutex>(e->lanes[i].mu);
+    e->fused_heads = on && hf_takes(fused_heads_plan(e)) ? 1 : 0;
+    return CATTUS_OK;
+}
+
+CATTUS_API int cattus_hip_fused_heads_effective(const cattus_eval* e, uint32_t* effective) {
+    if (!e || !effective) return fail(CATTUS_E_INVALID, "NULL argument");
+    *effective = e->fused_heads.load(std::memory_order_relaxed);
+    return CATTUS_OK;
+}
+
+CATTUS_API int cattus_hip_fused_heads_batches(cattus_eval* e, uint64_t* batches) {
+    if (!e || !batches) return fail(CATTUS_E_INVALID, "NULL argument");
+    *batches = e->fused_heads_batches.load(std::memory_order_relaxed);
     return CATTUS_OK;
 }
 

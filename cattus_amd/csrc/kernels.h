@@ -14,6 +14,7 @@
 #include "head_chain_rule.h"  // the short-chain form of the f32 FC pair: grid map, operand offsets, walk order, epilogues
 #include "t64r_rule.h"    // dtype f16r_resident: that tower in one LDS-resident launch -- who owns an element, the LDS buffers, the layer table
 #include "t64f_rule.h"    // dtype f32_resident: the exact f32 tower in one LDS-resident launch -- LDS plan, step table, ownership map, layer table
+#include "head_fuse_rule.h"  // cattus_hip_fused_heads: the f32 head convs in the tail of the resident f16 and f16r towers -- LDS plan, ownership, chain, hv index
 
 namespace cattus {
 
@@ -235,26 +236,27 @@ struct Tower64Layer {
 struct Tower64Args {
     const uint64_t* planes;      // [n][C][w64] bitboards
     const Tower64Layer* layers;  // device array [nlayers]: stem, then (conv1, conv2) per block
-    void* out;                   // bf16, optional: [rows][64] bf16 tower output, rows = boards * tower_slots(S); f16, required: the same in f32
+    void* out;                   // bf16, optional: [rows][64] bf16 tower output, rows = boards * tower_slots(S); f16: the same in f32, required unless the heads are fused
     unsigned* sat;               // f16: the evaluator's saturation counter (ConvOpts::saturated); bf16: not read
     uint32_t n, C, w64, S, nlayers;
-    // bf16 only, optional, fused K3: the two 1x1 head convs (+ folded BN + ReLU) on the resident tower output, written in the
-    // layout the head FC kernels read (HeadsMfma::hv)
-    const void* head_w;   // [32][64] bf16, value rows first, rows >= ocn zero
+    // optional, fused K3: the two 1x1 head convs (+ folded BN + ReLU) on the resident tower output, written in the
+    // layout the head FC kernels read (HeadsMfma::hv).  f16 (cattus_hip_fused_heads; head_fuse_rule.h): in f32, instead of `out`
+    const void* head_w;   // [32][64] bf16 (f16: f32), value rows first, rows >= ocn zero
     const float* head_b;  // [32]: entries >= ocn are not used
-    void* hv;             // head activations in the fragment-packed layout of HeadsMfma::hv, bf16
+    void* hv;             // head activations in the fragment-packed layout of HeadsMfma::hv, bf16 (f16: f32)
     uint32_t hv_pol, kvp, kpp, vhc, ocn;  // hv_pol: element offset of the policy part
 };
 // rows % 256 == 0; ch = 2: 128 rows per workgroup, ch = 4: one 64-slot board per workgroup (small batches; 128-slot
 // boards run as ch = 2).  layer_steps: with ch = 4 and boards of <= 63 pixels, one barrier per layer instead of three
-// (two layers of weights in LDS); same results.  act: Act::BF16, or Act::F16 with sat and out set and no head_w (the f32 head kernels read
-// out); anything else aborts.
+// (two layers of weights in LDS); same results.  act: Act::BF16, or Act::F16 with sat set and exactly one of out (the f32 head kernels read
+// it) and head_w + head_b + hv (the HEADS instances: the head convs in the tail, nothing written to out); anything else aborts.
 void launch_tower64(Act act, const Tower64Args& args, uint32_t rows, int ch, bool layer_steps, hipStream_t st,
                     hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 // K1hr resident (dtype f16r_resident; tower64_stream_kernel; t64r_rule.h has the ownership map, the LDS buffers and the layer table): the
 // Act::F16 launch above -- its arguments, layers (dtype f16r's = dtype f16's weights and [biases | inverse scales]; Tower64Layer::res as
 // t64r_layer().skip), workgroup shapes and LDS plan -- with the residual stream kept in f32 in the owning lanes' registers: the bits of
-// the per-layer f16r tower (launch_conv3x3_f16r and dtype f16's conv1).  args.sat and args.out required, no fused heads; anything else aborts.
+// the per-layer f16r tower (launch_conv3x3_f16r and dtype f16's conv1).  args.sat required, and exactly one of args.out and the fused heads'
+// head_w + head_b + hv, as for Act::F16 above; anything else aborts.
 void launch_tower64_stream(const Tower64Args& args, uint32_t rows, int ch, bool layer_steps, hipStream_t st, hipEvent_t ev_start = nullptr,
                            hipEvent_t ev_stop = nullptr);
 

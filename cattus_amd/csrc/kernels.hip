@@ -1489,10 +1489,18 @@ constexpr int tower64_lds_bytes(int ch, bool ls) { return ls ? 6 * V2_SLAB + 2 *
 // byte for byte: buffer 0 the operand copy f16(min(y, 65504)), buffer 1 the planes and then a block's middle activation.  Every
 // element is finished by f16r_finish, as in conv3x3_f16r_kernel; a conv1 is the f16 tower's layer.  Loader waves, weight ring, plane
 // expansion, address tables and fragment pipeline are shared: only the f16 epilogue branches on STREAM.
-// The body of the two __global__ functions below.
-template <typename T, int CH, bool BIG, bool LS, bool STREAM>
+// HEADS (T = _Float16 only; cattus_hip_fused_heads, head_fuse_rule.h): the last layer's epilogue stages its f32 rows in LDS instead of sending
+// them to A.out, and the consumer waves run head_conv_tile<float>'s chain on them in the tail (hf_head_convs): the stand-alone launch's bits in
+// hv.  Rows, head weights and biases lie in ring bytes that are dead behind the last step's barrier; the loader waves bring the operands in
+// under the last step and stay for one more barrier, which orders all three against the chain's reads.  A compile-time flag: the instances
+// without it are the code they were.
+// The body of the two __global__ functions below and of the HEADS instances' entry (Tower64Heads).
+template <typename T, int CH, bool BIG, bool LS, bool STREAM, bool HEADS = false>
 __device__ __forceinline__ void tower64_lds_tower(const Tower64Args A) {
     static_assert(NLOAD == 4, "512 threads: four consumer and four loader waves");
+    static_assert(!HEADS || std::is_same<T, _Float16>::value, "the bf16 tower fuses its heads unconditionally (A.head_w)");
+    constexpr HfLds HF = hf_lds_t64(CH, LS);
+    static_assert(V2_SLAB == HF_SLAB && HF.rows % 16 == 0 && HF.rows + HF.rows_bytes <= (LS ? 6 : 2) * V2_SLAB, "head_fuse_rule.h's plan lies in the dead slabs");
     static_assert(!LS || CH == 4, "layer steps: one board per workgroup only");
     static_assert(!STREAM || std::is_same<T, _Float16>::value, "the f32 residual stream belongs to the single-term f16 tower");
     constexpr int R_LDS_ACT = (LS ? 6 : 3) * V2_SLAB;
@@ -1610,6 +1618,7 @@ __device__ __forceinline__ void tower64_lds_tower(const Tower64Args A) {
                 else wait_vm_barrier<0>();
                 if (layer >= 1 && layer + 1 < nlayers) issue_layer(layer + 1);
             }
+            if constexpr (HEADS) hf_stage_operands(reinterpret_cast<const float*>(A.head_w), A.head_b, smem + HF.w, smem + HF.b, tid - 256);
             return;
         }
         for (int t = 0; t < T_total; t++) {
@@ -1619,6 +1628,7 @@ __device__ __forceinline__ void tower64_lds_tower(const Tower64Args A) {
             if (t + 2 < T_total) issue_w(t + 2);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (HEADS) hf_stage_operands(reinterpret_cast<const float*>(A.head_w), A.head_b, smem + HF.w, smem + HF.b, tid - 256);
         return;
     }
 
@@ -1834,6 +1844,8 @@ __device__ __forceinline__ void tower64_lds_tower(const Tower64Args A) {
             // come from t64r_own, the map that names the element a register holds in every layer alike.
             const T64rLayer rl = t64r_layer((uint32_t)layer, t64r_blocks((uint32_t)nlayers));
             const bool stream_layer = STREAM && rl.stream;
+            // HEADS: where the last layer's f32 values go instead of A.out -- four consecutive channels of a workgroup row, staged for the chain
+            auto stage = [&](int row, int channel, const f32x4& v) { *reinterpret_cast<f32x4*>(smem + HF.rows + hf_row_offset(row, channel)) = v; };
             if (stream_layer) {
                 unsigned nsat = 0;
                 const int lane_now = lane + opaque;  // (0: keeps the sixteen addresses below from being hoisted out of the layer loop, where the stream needs the registers)
@@ -1852,8 +1864,10 @@ __device__ __forceinline__ void tower64_lds_tower(const Tower64Args A) {
                                 sreg[cb][pb][g * 4 + q] = o.stream;
                                 yv[q] = o.stream, cv[q] = o.copy, nsat += o.counted ? 1u : 0u;
                             }
-                            if (rl.last) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(A.out) + t64r_out_index((size_t)row0, own)) = yv;
-                            else *reinterpret_cast<tx4*>(smem + obase + t64r_lds_offset(own)) = cv;
+                            if (rl.last) {
+                                if constexpr (HEADS) stage(own.row, own.channel, yv);
+                                else *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(A.out) + t64r_out_index((size_t)row0, own)) = yv;
+                            } else *reinterpret_cast<tx4*>(smem + obase + t64r_lds_offset(own)) = cv;
                         }
                 if (!rl.last && nsat) atomicAdd(A.sat, nsat);  // note_saturation's rule: one atomic add on the clamp path only
             } else {  // (not indented: the code as it was)
@@ -1883,6 +1897,12 @@ __device__ __forceinline__ void tower64_lds_tower(const Tower64Args A) {
                             y[j] = pvalid[pb] && v > 0.0f ? v : 0.0f;
                         }
                         if (last) {
+                            if constexpr (HEADS) {
+                                const int row = rb * 64 + (pb0 + pb) * 32 + r, ch0 = coutb + cb * 32 + h * 4;
+                                stage(row, ch0 + (g2 * 2) * 8, *reinterpret_cast<f32x4*>(y));
+                                stage(row, ch0 + (g2 * 2 + 1) * 8, *reinterpret_cast<f32x4*>(y + 4));
+                                continue;
+                            }
                             float* of = reinterpret_cast<float*>(A.out) + ((size_t)row0 + rb * 64 + (pb0 + pb) * 32 + r) * 64 + coutb + cb * 32 + h * 4;
                             *reinterpret_cast<f32x4*>(of + (g2 * 2) * 8) = *reinterpret_cast<f32x4*>(y);
                             *reinterpret_cast<f32x4*>(of + (g2 * 2 + 1) * 8) = *reinterpret_cast<f32x4*>(y + 4);
@@ -1957,7 +1977,13 @@ __device__ __forceinline__ void tower64_lds_tower(const Tower64Args A) {
     }
     STAMP(2);
 
-    if constexpr (!F16T) {  // f16: the last layer's epilogue has stored the f32 rows; the f32 head kernels follow as launches of their own
+    if constexpr (HEADS) {
+        // every consumer's staged rows and the loaders' operands are in LDS before any chain reads them: all eight waves meet here
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        asm volatile("" : "+v"(opaque));  // (0: keeps what the chain derives from the lane out of the layer loop's live registers)
+        hf_head_convs<CH>(smem, HF, [&](int row, int u, int h) { return HF.rows + hf_row_frag(row, u, h); }, wave, lane + opaque, row0, SLOTS_PER_BOARD, A);
+    }
+    if constexpr (!F16T) {  // f16: the last layer's epilogue has stored the f32 rows; the f32 head kernels follow as launches of their own, or HEADS has run them above
     // ---- the two 1x1 head convs on the resident tower output (K3 fused; same MFMA order as head_conv_tile) ----
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // the loader waves have left: live waves only
     const int fin = (nlayers & 1) ? 0 : 1;  // the stem and every second conv of a block write buffer 0
@@ -2021,8 +2047,17 @@ __global__ void __launch_bounds__(512, 2) tower64_stream_kernel(Tower64Args A) {
     tower64_lds_tower<_Float16, CH, BIG, LS, true>(A);
 }
 
-// Every instance that exists, f(kernel, LDS bytes, CH, BIG, LS): one board per workgroup (CH = 4) on 64-slot boards only, one barrier per
-// layer (LS) with CH = 4 only.  T: the element type of tower64_lds_kernel (__bf16, _Float16), or Tower64Stream for tower64_stream_kernel.
+// The HEADS instance of either f16 kernel above (cattus_hip_fused_heads), entered through tower_heads_kernel (device_common.h)
+template <bool F32_STREAM, int CH, bool BIG, bool LS>
+struct Tower64Heads {
+    typedef Tower64Args Args;
+    static constexpr int MIN_WAVES = 2;
+    static __device__ __forceinline__ void run(const Args& A) { tower64_lds_tower<_Float16, CH, BIG, LS, F32_STREAM, true>(A); }
+};
+
+// Every instance that exists, f(kernel, LDS bytes, CH, BIG, LS, HEADS): one board per workgroup (CH = 4) on 64-slot boards only, one barrier per
+// layer (LS) with CH = 4 only; the head convs in the tail (HEADS) on the f16 families only -- the same shapes and the same LDS bytes.
+// T: the element type of tower64_lds_kernel (__bf16, _Float16), or Tower64Stream for tower64_stream_kernel.
 struct Tower64Stream {};
 template <typename T, class F>
 static void for_each_tower64(F&& f) {
@@ -2030,8 +2065,10 @@ static void for_each_tower64(F&& f) {
         constexpr int CH = decltype(ch)::value;
         constexpr bool BIG = decltype(big)::value, LS = decltype(ls)::value;
         if constexpr (CH == 4 ? !BIG : !LS) {
-            if constexpr (std::is_same<T, Tower64Stream>::value) f(&tower64_stream_kernel<CH, BIG, LS>, tower64_lds_bytes(CH, LS), ch, big, ls);
-            else f(&tower64_lds_kernel<T, CH, BIG, LS>, tower64_lds_bytes(CH, LS), ch, big, ls);
+            if constexpr (std::is_same<T, Tower64Stream>::value) f(&tower64_stream_kernel<CH, BIG, LS>, tower64_lds_bytes(CH, LS), ch, big, ls, std::false_type{});
+            else f(&tower64_lds_kernel<T, CH, BIG, LS>, tower64_lds_bytes(CH, LS), ch, big, ls, std::false_type{});
+            if constexpr (!std::is_same<T, __bf16>::value)
+                f(&tower_heads_kernel<Tower64Heads<std::is_same<T, Tower64Stream>::value, CH, BIG, LS>>, tower64_lds_bytes(CH, LS), ch, big, ls, std::true_type{});
         }
     }); }); });
 }
@@ -2042,16 +2079,24 @@ static void launch_tower64_of(const Tower64Args& args, uint32_t rows, int ch, bo
     const bool want_big = tower_slots(args.S) == 128;
     const int want_ch = ch == 4 && !want_big ? 4 : 2;
     const bool want_ls = want_ch == 4 && layer_steps && args.S * args.S <= 63;
-    for_each_tower64<T>([&](auto kernel, int lds, auto c, auto big, auto ls) {
-        if (c == want_ch && big == want_big && ls == want_ls)
+    const bool want_heads = !std::is_same<T, __bf16>::value && args.head_w;  // (the bf16 kernel reads head_w at run time)
+    for_each_tower64<T>([&](auto kernel, int lds, auto c, auto big, auto ls, auto heads) {
+        if (c == want_ch && big == want_big && ls == want_ls && heads == want_heads)
             hipExtLaunchKernelGGL(kernel, dim3(rows / (256 / c)), dim3(512), lds, st, ev_start, ev_stop, 0, args);
     });
 }
 
+// what the f16 instances serve: the saturation counter, and the tower's output either as f32 rows in memory (the instances without HEADS) or
+// run through the head convs in the tail (HEADS: every operand of theirs, and no rows) -- never both, never neither, never half the operands
+static bool tower64_f16_args_served(const Tower64Args& args) {
+    const bool heads = args.head_w && args.head_b && args.hv, no_heads = !args.head_w && !args.head_b && !args.hv;
+    return args.sat && ((args.out && no_heads) || (!args.out && heads));
+}
+
 void launch_tower64(Act act, const Tower64Args& args, uint32_t rows, int ch, bool layer_steps, hipStream_t st, hipEvent_t ev_start,
                     hipEvent_t ev_stop) {
-    if (act != Act::BF16 && !(act == Act::F16 && args.sat && args.out && !args.head_w)) {
-        fprintf(stderr, "cattus: launch_tower64: bf16, or f16 with Tower64Args::sat and ::out and no fused heads\n");
+    if (act != Act::BF16 && !(act == Act::F16 && tower64_f16_args_served(args))) {
+        fprintf(stderr, "cattus: launch_tower64: bf16, or f16 with Tower64Args::sat and either ::out or the fused heads' ::head_w, ::head_b and ::hv\n");
         abort();
     }
     if (act == Act::F16) launch_tower64_of<_Float16>(args, rows, ch, layer_steps, st, ev_start, ev_stop);
@@ -2059,8 +2104,8 @@ void launch_tower64(Act act, const Tower64Args& args, uint32_t rows, int ch, boo
 }
 
 void launch_tower64_stream(const Tower64Args& args, uint32_t rows, int ch, bool layer_steps, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    if (!(args.sat && args.out && !args.head_w)) {
-        fprintf(stderr, "cattus: launch_tower64_stream: needs Tower64Args::sat and ::out and no fused heads\n");
+    if (!tower64_f16_args_served(args)) {
+        fprintf(stderr, "cattus: launch_tower64_stream: needs Tower64Args::sat and either ::out or the fused heads' ::head_w, ::head_b and ::hv\n");
         abort();
     }
     launch_tower64_of<Tower64Stream>(args, rows, ch, layer_steps, st, ev_start, ev_stop);
@@ -2141,6 +2186,16 @@ constexpr bool hc_order_is_kperm() {
     return true;
 }
 static_assert(hc_order_is_kperm(), "head_chain_rule.h's order is kperm");
+// and so do the head convs in the resident towers' tails (head_fuse_rule.h), which write hv at frag_packed_index<float>
+constexpr bool hf_rule_is_head_conv_tile() {
+    for (uint32_t t = 0; t < HF_K; t++)
+        if (hf_term_k(t) != kperm(t)) return false;
+    for (uint32_t row = 0; row < 96; row += 5)
+        for (uint32_t k = 0; k < 1024; k += 3)
+            if (hf_packed_f32(row, k, 1024) != frag_packed_index<float>(row, k, 1024)) return false;
+    return true;
+}
+static_assert(hf_rule_is_head_conv_tile(), "head_fuse_rule.h's order is kperm, its hv index frag_packed_index<float>");
 
 // ---- MFMA path: D[i][j] = sum_k P[i][k] * Q[j][k], K contiguous in both operands ------------
 enum { EPI_FC1 = 1, EPI_POLICY = 2 };

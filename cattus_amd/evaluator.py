@@ -76,6 +76,9 @@ ABI_SYMBOLS = [
     "cattus_hip_head_chain",
     "cattus_hip_head_chain_leaves",
     "cattus_hip_head_chain_batches",
+    "cattus_hip_fused_heads",
+    "cattus_hip_fused_heads_effective",
+    "cattus_hip_fused_heads_batches",
     "cattus_hip_stream_range",
     "cattus_hip_create_calibrated",
     "cattus_hip_verify",
@@ -95,6 +98,10 @@ ABI_SYMBOLS = [
     "cattus_hip_stem_input",  # include/cattus_hip_diag.h
     "cattus_hip_splitk_plan",  # include/cattus_hip_diag.h
 ]
+
+# Symbols an OLDER build of the library may lack.  Only a build selected with CATTUS_HIP_LIB may (scripts/fused_heads_time.py times the parent
+# commit's library that way); the package's own library must have every symbol.  Calling a method whose symbol is absent raises AttributeError.
+ABI_NEWER_SYMBOLS = ("cattus_hip_fused_heads", "cattus_hip_fused_heads_effective", "cattus_hip_fused_heads_batches")
 
 
 class CattusHipError(RuntimeError):
@@ -255,6 +262,11 @@ def load_library():
     L.cattus_hip_head_chain.argtypes = [vp, C.c_uint32]
     L.cattus_hip_head_chain_leaves.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.cattus_hip_head_chain_batches.argtypes = [vp, C.POINTER(C.c_uint64)]
+    absent = [name for name in ABI_NEWER_SYMBOLS if not hasattr(L, name)] if "CATTUS_HIP_LIB" in os.environ else []
+    if "cattus_hip_fused_heads" not in absent:
+        L.cattus_hip_fused_heads.argtypes = [vp, C.c_uint32]
+        L.cattus_hip_fused_heads_effective.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.cattus_hip_fused_heads_batches.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.cattus_hip_stream_shift.argtypes = [vp]
     L.cattus_hip_stream_shifts.argtypes = [vp, C.POINTER(C.c_int), C.c_uint32]
     L.cattus_hip_stem_input.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -271,6 +283,8 @@ def load_library():
     L.cattus_hip_tap.argtypes = [vp, u64p, C.c_uint32, C.c_uint32, f32p, f32p, f32p]
     L.cattus_hip_trace.argtypes = [vp, vp, C.c_size_t, u64p, C.c_uint32, vp, C.c_uint32, f32p, f32p]
     for name in ABI_SYMBOLS:
+        if name in absent:
+            continue
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("cattus_hip_last_error", "cattus_hip_version", "cattus_hip_runtime_note", "cattus_hip_host_alloc",
                                                    "cattus_hip_tower_kernel"):
@@ -353,6 +367,7 @@ class HipEvaluator:
         verify_every: int = 0,
         tail_leaves: int = 0,
         head_chain_leaves: int = 0,
+        fused_heads: bool = False,
     ):
         """dtype: "f32" | "bf16" | "f16x2" | "f16" | "f16w" | "f32w" (cattus_dtype).  "f16w" is the single-term f16 tower in Winograd F(2x2,3x3) form with an f32 stream: an 8x8
         board, at least one residual block, a multiple of 64 filters >= 128, tower_form "auto" or "winograd" (both mean it); anything else is refused.
@@ -379,7 +394,10 @@ class HipEvaluator:
         tail_leaves: k >= 1 runs batches of at most k leaves of the Winograd F(2x2,3x3) tower on its small-tile kernel (cattus_eval_config.tail_leaves:
         the same bits, more workgroups for a short batch); ignored on every other plan (``tail_leaves()`` says what holds); 0, the default: off.
         head_chain_leaves: k >= 1 runs the f32 heads' FC pair of batches of at most k leaves as short fmaf chains (``head_chain``: the same bits);
-        ignored where the heads are not the f32 MFMA heads (``head_chain_leaves()`` says what holds); 0, the default: off."""
+        ignored where the heads are not the f32 MFMA heads (``head_chain_leaves()`` says what holds); 0, the default: off.
+        fused_heads: True runs the two 1x1 head convs in the tail of the resident "f16" (tower_form "resident") and "f16r_resident" tower
+        launch instead of a launch of their own (``fused_heads``: the same bits); ignored on every other plan (``fused_heads_effective()`` says what
+        holds); False, the default: off."""
         self.desc: NetDesc = parse_header(blob)
         self.batch_size = int(batch_size)
         self.plane_words = int(plane_words)
@@ -417,6 +435,8 @@ class HipEvaluator:
         try:
             if head_chain_leaves:
                 self.head_chain(head_chain_leaves)
+            if fused_heads:
+                self.fused_heads(True)
             if verify_every:
                 self.verify(verify_every)
         except Exception:
@@ -720,6 +740,25 @@ class HipEvaluator:
         """Batches whose FC pair took the chain form since the evaluator was created."""
         k = C.c_uint64()
         _check(self._lib.cattus_hip_head_chain_batches(self._h, C.byref(k)))
+        return int(k.value)
+
+    def fused_heads(self, on: bool) -> None:
+        """``cattus_hip_fused_heads``: the resident "f16" (tower_form "resident") and "f16r_resident" towers run the two 1x1 head convs in the tail of their one
+        launch, on the f32 rows still in LDS, instead of writing the rows to memory for ``head_conv_kernel<float>`` (the same bits; two launches per pass
+        instead of three); False: the launch of their own, the default.  Accepted and ignored on every other plan -- "bf16" and "f16x2" resident towers
+        run the head convs in their tails always, "f32_resident" keeps the launch."""
+        _check(self._lib.cattus_hip_fused_heads(self._h, 1 if on else 0))
+
+    def fused_heads_effective(self) -> bool:
+        """The ``fused_heads`` setting as it holds for this evaluator: False where it is off or ignored."""
+        k = C.c_uint32()
+        _check(self._lib.cattus_hip_fused_heads_effective(self._h, C.byref(k)))
+        return bool(k.value)
+
+    def fused_heads_batches(self) -> int:
+        """Passes that ran the head convs in the tower's tail since the evaluator was created."""
+        k = C.c_uint64()
+        _check(self._lib.cattus_hip_fused_heads_batches(self._h, C.byref(k)))
         return int(k.value)
 
     def tail_batches(self) -> int:

@@ -640,6 +640,8 @@ def main(argv=None):
     tail_leaves = int(inf.get("tail_leaves", 0))
     # optional: the f32 heads' FC pair of batches of at most this many leaves as short fmaf chains (cattus_hip_head_chain: the same bits); absent or 0: off
     head_chain_leaves = int(inf.get("head_chain_leaves", 0))
+    # optional: the two 1x1 head convs in the tail of the resident f16 / f16r tower launch (cattus_hip_fused_heads: the same bits); absent or false: off
+    fused_heads = bool(inf.get("fused_heads", False))
     # optional: the form of the f16x2 tower (cattus_tower_form): "auto" (absent), "direct", "winograd", "winograd_f4", or "direct_splitk" -- the
     # direct form for batches of a few leaves, the reference's threads: 8, batch_size: 1 (include/cattus_hip.h); or "resident": the one-launch
     # LDS-resident tower of a network with at most 64 filters, for dtype f16 the only way to it
@@ -649,7 +651,7 @@ def main(argv=None):
         blob = Path(path).read_bytes()
         return HipEvaluator(blob, batch_size=engine["model"]["batch_size"], plane_words=info["plane_words"],
                             dtype=inf.get("dtype", "f16x2"), device=inf.get("device", 0), verify_every=verify_every, tail_leaves=tail_leaves, head_chain_leaves=head_chain_leaves,
-                            tower_form=tower_form)
+                            tower_form=tower_form, fused_heads=fused_heads)
 
     ev1 = load(args.model1_path)
     same = os.path.abspath(args.model1_path) == os.path.abspath(args.model2_path)

@@ -616,6 +616,22 @@ int cattus_hip_head_chain_leaves(const cattus_eval* e, uint32_t* effective);
 /* Batches whose FC pair took the chain form since the evaluator was created, through any entry point (as cattus_hip_tail_batches). */
 int cattus_hip_head_chain_batches(cattus_eval* e, uint64_t* batches);
 
+/* The two 1x1 head convs in the tail of the resident f16 and f16r towers.  0 (the default): nothing changes.  on != 0: an unobserved pass launches
+ * the HEADS instance of the plan's resident kernel (tower64_lds_tower<..., HEADS>): the last layer's f32 rows stay in LDS,
+ * the consumer waves run head_conv_tile<float>'s chain on them (head weights and biases brought into dead ring bytes under the last layer) and write hv;
+ * the tower's output rows are not written to memory and head_conv_kernel<float> is not launched -- two launches per pass instead of three.  THE BITS DO
+ * NOT CHANGE: every logit, value, prior and the saturation count equal what the evaluator returns with 0, through every entry point
+ * (tests/test_fused_heads_gpu.py).  Effective (cattus_hip_fused_heads_effective reports 1) on CATTUS_DTYPE_F16 under CATTUS_TOWER_RESIDENT and
+ * CATTUS_DTYPE_F16R_RESIDENT (cattus_hip_tower_kernel, which this setting does not change); accepted and ignored (0) everywhere else: the bf16 and
+ * f16x2 resident towers, which run the head convs in their tails always, and CATTUS_DTYPE_F32_RESIDENT, whose kernel has no such instance.  Waits
+ * for the batches in flight.  Composes with cattus_hip_head_chain.  Observed passes (tap, trace), cattus_hip_time_tower, the verification shadow and the
+ * calibration's temporary evaluator keep the head conv launch.  UNMEASURED (scripts/fused_heads_time.py is the method, DESIGN.md
+ * section 3, K3r, has the estimate): recommended nowhere until it is.  The default stays 0. */
+int cattus_hip_fused_heads(cattus_eval* e, uint32_t on);
+int cattus_hip_fused_heads_effective(const cattus_eval* e, uint32_t* effective);
+/* Passes that ran the head convs in the tower's tail since the evaluator was created, through any entry point (as cattus_hip_tail_batches). */
+int cattus_hip_fused_heads_batches(cattus_eval* e, uint64_t* batches);
+
 const char* cattus_hip_last_error(void);
 const char* cattus_hip_version(void);
 /* What the last cattus_hip_create found for HIP_FORCE_DEV_KERNARG (the host process exports it before HIP initialises:
